@@ -59,7 +59,105 @@ def parse_args():
                    choices=["auto", "cpu", "gpu"])
     p.add_argument("--inference-worker", type=str, default="process",
                    choices=["thread", "process"])
-    return p.parse_args()
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="write what the last timed step computed to "
+                        "DIR/<name>.npy (see _fixed_batch / _dump_outputs)")
+    p.add_argument("--full", action="store_true",
+                   help="also report everything beyond the headline figure: "
+                        "setup-phase and per-section learner timings and "
+                        "actor production (stderr)")
+    args = p.parse_args()
+    if args.dump_outputs is not None and args.steps < 1:
+        p.error("--dump-outputs needs at least one timed step")
+    return args
+
+
+# --dump-outputs ------------------------------------------------------------
+# The timed path is fed by live actor processes, so its batches depend on
+# process scheduling and differ from run to run.  To make two builds
+# comparable output for output, the LAST timed step of a --dump-outputs run
+# still pulls its batch through the whole pipeline, but then learns from a
+# fixed seeded batch of the same shapes, starting from the seeded initial
+# weights and a zeroed optimizer state.  What that step hands its caller
+# (the four loss scalars, the clipped flat gradient and the updated flat
+# weights) is written out.
+
+_DUMP_SEED = 20240229
+_DUMP_MAX_ELEMS = 7 * 1024 * 1024  # per array; two float32 arrays < 64 MB
+
+
+def _fixed_batch(like, num_actions):
+    """A seeded batch with the keys, shapes, dtypes and device of ``like``."""
+    g = torch.Generator(device="cpu").manual_seed(_DUMP_SEED)
+    out = {}
+    for name in sorted(like):
+        ref = like[name]
+        if ref.dtype == torch.uint8:
+            t = torch.randint(0, 256, ref.shape, dtype=torch.uint8,
+                              generator=g)
+        elif ref.dtype == torch.bool:
+            t = torch.rand(ref.shape, generator=g) < 0.02
+        elif ref.dtype.is_floating_point:
+            t = torch.randn(ref.shape, generator=g).to(ref.dtype)
+            if name == "core_state":
+                t.mul_(0.1)
+        else:  # action ids
+            t = torch.randint(0, num_actions, ref.shape, dtype=ref.dtype,
+                              generator=g)
+        out[name] = t.to(ref.device)
+    return out
+
+
+def _dump_outputs(path, stats, trainer):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().float().reshape(-1).cpu().numpy()
+              for k, v in stats.items()}
+    arrays["flat_grad"] = trainer.flat.flat_grad.detach().float().cpu().numpy()
+    arrays["flat_params"] = trainer.flat.flat.detach().float().cpu().numpy()
+    rng = np.random.default_rng(_DUMP_SEED)
+    for name, a in arrays.items():
+        if a.size > _DUMP_MAX_ELEMS:  # fixed seeded sample of a large output
+            idx = np.sort(rng.choice(a.size, _DUMP_MAX_ELEMS, replace=False))
+            a = a[idx]
+        np.save(os.path.join(path, f"{name}.npy"),
+                np.ascontiguousarray(a, dtype=np.float32))
+
+
+_TUNED_DB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                             "tuning", "miopen")
+
+
+def _install_tuned_perf_db(user_db_dir):
+    """Merge the repository's tuned MIOpen perf-db records (tuning/miopen/,
+    the solver parameters MIOpen's own search settled on for the default
+    learner shapes) into the user db.  Without them every run in a fresh
+    user db repeats that search (~45 s) before its first step.  Files are
+    named by GPU arch and MIOpen version, so another version ignores them
+    and tunes as before; records already in the user db are kept."""
+    if not user_db_dir or not os.path.isdir(_TUNED_DB_DIR):
+        return
+    for fname in sorted(os.listdir(_TUNED_DB_DIR)):
+        if not fname.endswith(".udb.txt"):
+            continue
+        dst = os.path.join(user_db_dir, fname)
+        try:
+            with open(os.path.join(_TUNED_DB_DIR, fname)) as f:
+                ours = [ln for ln in f.read().splitlines() if "=" in ln]
+            have = []
+            if os.path.exists(dst):
+                with open(dst) as f:
+                    have = [ln for ln in f.read().splitlines() if ln]
+            keys = {ln.split("=", 1)[0] for ln in have}
+            new = [ln for ln in ours if ln.split("=", 1)[0] not in keys]
+            if not new:
+                continue
+            tmp = f"{dst}.{os.getpid()}.tmp"
+            with open(tmp, "w") as f:
+                f.write("\n".join(have + new) + "\n")
+            os.replace(tmp, dst)  # atomic: ranks may race here
+        except OSError:
+            pass  # read-only db dir: MIOpen tunes by itself as before
 
 
 def main():
@@ -67,9 +165,39 @@ def main():
     # has been observed to settle on naive bf16 conv kernels on fresh boxes),
     # and ONE shared find-cache db across all ranks of a node.
     os.environ.setdefault("MIOPEN_FIND_MODE", "1")
-    os.environ.setdefault("MIOPEN_USER_DB_PATH", "/tmp/scalerl_miopen")
-    os.makedirs(os.environ["MIOPEN_USER_DB_PATH"], exist_ok=True)
+    if "MIOPEN_USER_DB_PATH" not in os.environ:
+        # per user, next to MIOpen's own kernel cache: both then persist
+        # together from one run to the next
+        for db in (os.path.join(os.path.expanduser("~"), ".cache",
+                                "scalerl_amd", "miopen"),
+                   "/tmp/scalerl_miopen"):
+            try:
+                os.makedirs(db, exist_ok=True)
+            except OSError:
+                continue
+            if os.access(db, os.W_OK):
+                os.environ["MIOPEN_USER_DB_PATH"] = db
+                break
+    else:
+        os.makedirs(os.environ["MIOPEN_USER_DB_PATH"], exist_ok=True)
+    _install_tuned_perf_db(os.environ.get("MIOPEN_USER_DB_PATH"))
     args = parse_args()
+    if args.dtype == "bf16":
+        # The find re-times every applicable solver in every process.  At
+        # the bf16 encoder shapes the im2col-GEMM and naive direct solvers
+        # run 200-1000x slower than the implicit-GEMM winners (500-1400 ms
+        # vs 0.4-2.2 ms per call) and made up ~95 of the ~100 s a find
+        # took; they never win, so leaving them out changes no choice.
+        for var in ("MIOPEN_DEBUG_CONV_GEMM",
+                    "MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_FWD",
+                    "MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_BWD",
+                    "MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_WRW"):
+            os.environ.setdefault(var, "0")
+    marks = [("start", time.perf_counter())]  # setup phases (--full report)
+
+    def mark(name):
+        marks.append((name, time.perf_counter()))
+
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -132,8 +260,10 @@ def main():
         total_steps=1 << 60, disable_checkpoint=True,
         output_dir="/tmp/scalerl_bench")
 
+    mark("imports+args")
     trainer = ImpalaTrainer(cfg, device=device)
     trainer.rank = rank
+    mark("trainer init (rollout store)")
     if trainer._mp_ctx == "fork":
         # pure-CPU path: fork actors BEFORE any device init
         trainer.start_actors()
@@ -144,7 +274,9 @@ def main():
     # spawn the inference worker + actors (capture must precede any other
     # process submitting on this GPU — see ImpalaTrainer.setup_learner)
     trainer.setup_learner()
+    mark("learner setup (pin, graph capture)")
     trainer.start_actors()
+    mark("start actors")
 
     def barrier_sync():
         if world > 1:
@@ -152,16 +284,47 @@ def main():
         if use_cuda:
             torch.cuda.synchronize()
 
+    dump = args.dump_outputs is not None
+    if dump:
+        init_flat = trainer.flat.flat.detach().clone()
+
     for _ in range(args.warmup):
         trainer.train_iteration()
     trainer.reset_timings()  # drop first-iteration autotune/compile spikes
+    mark("warmup")
 
+    # with --dump-outputs the last timed step is run apart from the others,
+    # with the clock stopped while its fixed inputs are put in place
     barrier_sync()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1 if dump else args.steps):
         trainer.train_iteration()
     barrier_sync()
     elapsed = time.perf_counter() - t0
+
+    if dump:
+        t0 = time.perf_counter()
+        trainer.timings.reset()
+        live = trainer.next_batch()
+        barrier_sync()
+        elapsed += time.perf_counter() - t0
+
+        fixed = _fixed_batch(live, trainer.num_actions)
+        with torch.no_grad():
+            trainer.flat.flat.copy_(init_flat)
+            trainer.optimizer.square_avg.zero_()
+            if trainer.optimizer.momentum_buf is not None:
+                trainer.optimizer.momentum_buf.zero_()
+
+        barrier_sync()
+        t0 = time.perf_counter()
+        trainer.timings.reset()
+        stats = trainer.learn_step(fixed)
+        barrier_sync()
+        elapsed += time.perf_counter() - t0
+        if rank == 0:
+            _dump_outputs(args.dump_outputs, stats, trainer)
+    mark("timed steps")
 
     # max over ranks (the slowest rank defines whole-job time)
     if world > 1:
@@ -175,13 +338,18 @@ def main():
     value = total_env_steps / elapsed
 
     if rank == 0:
-        import sys
-        produced = trainer.step_counter.value
-        print(f"[bench] learner timings (s/iter means):\n"
-              f"{trainer.timings.summary('  ')}\n"
-              f"[bench] actor production during run: {produced} env-steps "
-              f"({produced / elapsed:,.0f}/s incl. warmup overlap)",
-              file=sys.stderr)
+        if args.full:
+            import sys
+            produced = trainer.step_counter.value
+            phases = "\n".join(
+                f"  {name}: {t1 - t0:.2f} s"
+                for (_, t0), (name, t1) in zip(marks, marks[1:]))
+            print(f"[bench] run phases:\n{phases}\n"
+                  f"[bench] learner timings (s/iter means):\n"
+                  f"{trainer.timings.summary('  ')}\n"
+                  f"[bench] actor production during run: {produced} "
+                  f"env-steps ({produced / elapsed:,.0f}/s incl. warmup "
+                  f"overlap)", file=sys.stderr)
         result = {
             "metric": "env_steps_per_sec",
             "value": round(value, 1),

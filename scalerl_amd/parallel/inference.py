@@ -155,12 +155,15 @@ def inference_worker(device_index: int, model_kwargs: Dict, slots: InferenceSlot
     max_batch_actors = max_batch_actors or A
     seen_version = -1
 
-    # device staging for a batched round
-    obs_d = torch.empty((A, E, *slots.obs.shape[2:]), dtype=torch.uint8,
+    # device staging for a batched round.  Zero-filled, not empty: every
+    # round forwards ALL rows, and rows of actors that have not requested
+    # yet must hold valid inputs — an uninitialized last_action is an
+    # out-of-range index for the one-hot scatter (an out-of-bounds write)
+    obs_d = torch.zeros((A, E, *slots.obs.shape[2:]), dtype=torch.uint8,
                         device=device)
-    rew_d = torch.empty((A, E), device=device)
-    done_d = torch.empty((A, E), dtype=torch.bool, device=device)
-    lastact_d = torch.empty((A, E), dtype=torch.int64, device=device)
+    rew_d = torch.zeros((A, E), device=device)
+    done_d = torch.zeros((A, E), dtype=torch.bool, device=device)
+    lastact_d = torch.zeros((A, E), dtype=torch.int64, device=device)
 
     nonlocal_state = {"seen_version": seen_version}
 

@@ -609,8 +609,12 @@ class ImpalaTrainer:
                 self.inf_req_q.put_nowait(None)
             except Exception:
                 pass
+        # one shared grace period: an actor that is mid-rollout blocks on its
+        # inference semaphore once the worker is gone and never sees its
+        # pill, so a per-actor timeout would add up over all of them
+        deadline = time.time() + 2.0
         for p in self.actors:
-            p.join(timeout=2.0)
+            p.join(timeout=max(0.0, deadline - time.time()))
             if p.is_alive():
                 p.terminate()
         self.actors.clear()

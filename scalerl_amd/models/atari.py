@@ -23,7 +23,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..ops import MaskedLSTM
+from ..ops import MaskedLSTM, frame_cast
 
 
 class AtariNet(nn.Module):
@@ -69,7 +69,13 @@ class AtariNet(nn.Module):
             h = native_conv(2, h, self.conv2.weight, self.conv2.bias)
             h = native_conv(3, h, self.conv3.weight, self.conv3.bias)
             return F.relu(self.fc(torch.flatten(h, 1)))
-        x = x.float() / 255.0
+        if (x.is_cuda and x.dtype == torch.uint8 and
+                frame_cast.bf16_autocast_active()):
+            # autocast would cast the fp32 quotient to bf16 for conv1
+            # anyway: one fused pass, same bits
+            x = frame_cast.frame_to_bf16(x)
+        else:
+            x = x.float() / 255.0
         x = F.relu(self.conv1(x))
         x = F.relu(self.conv2(x))
         x = F.relu(self.conv3(x))

@@ -35,9 +35,10 @@ def hip_sources():
 def build(verbose: bool = True, arch: str = "gfx950") -> str:
     """Compile csrc/*.hip → _hip_ops.so in-tree.  Idempotent (mtime check)."""
     srcs = hip_sources()
-    hdr = os.path.join(_CSRC, "common.h")
+    hdrs = sorted(
+        os.path.join(_CSRC, f) for f in os.listdir(_CSRC) if f.endswith(".h"))
     if os.path.exists(_SO_PATH):
-        newest = max(os.path.getmtime(p) for p in srcs + [hdr])
+        newest = max(os.path.getmtime(p) for p in srcs + hdrs)
         if os.path.getmtime(_SO_PATH) >= newest:
             return _SO_PATH
     hipcc = os.environ.get("HIPCC", "hipcc")
@@ -68,10 +69,12 @@ def _declare(lib: ctypes.CDLL) -> None:
         "per_update": [P, L, P, P, L, P],
         "per_sample": [P, L, L, P, L, P, P, P],
         "per_leaf_min": [P, L, L, P, P],
-        "lstm_pointwise_fwd": [P, P, P, P, L, L, P],
-        "lstm_pointwise_bwd": [P, P, P, P, P, P, P, L, L, P],
-        "masked_lstm_seq_fwd": [P, P, P, P, P, P, P, P, P, P, L, L, L, P],
+        "lstm_mask_rows": [P, P, P, P, P, L, L, P],
+        "lstm_cell_fwd": [P, P, P, P, P, P, P, L, L, P],
+        "lstm_cell_bwd": [P, P, P, P, P, P, P, P, P, L, L, P],
+        "masked_lstm_seq_fwd": [P, P, P, P, P, P, P, P, P, L, L, L, P],
         "masked_lstm_seq_bwd": [P, P, P, P, P, P, P, P, P, P, L, L, L, P],
+        "frame_cast_u8_bf16": [P, P, L, P],
     }
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)

@@ -29,25 +29,13 @@ _c = ctypes.c_void_p
 
 def _pointwise_fwd(gates: torch.Tensor, c_prev: torch.Tensor,
                    out_h: torch.Tensor = None, out_c: torch.Tensor = None):
-    """Returns (h, c); `gates` is overwritten with activated gates.  When
-    ``out_h/out_c`` are given the results are written there (one fewer
-    launch per step on the hot path)."""
-    B, H4 = gates.shape
-    H = H4 // 4
-    if gates.is_cuda:
-        h = out_h if out_h is not None else torch.empty(
-            B, H, device=gates.device, dtype=torch.float32)
-        c = out_c if out_c is not None else torch.empty_like(h)
-        ret = _backend.lib().lstm_pointwise_fwd(
-            _c(gates.data_ptr()), _c(c_prev.data_ptr()), _c(h.data_ptr()),
-            _c(c.data_ptr()), B, H, _backend.current_stream())
-        _backend.check(ret, "lstm_pointwise_fwd")
-        return h, c
+    """CPU oracle of one cell step.  Returns (h, c); `gates` is overwritten
+    with activated gates, matching the GPU kernel's in-place contract."""
     i, f, g, o = gates.chunk(4, dim=1)
     i, f, g, o = i.sigmoid(), f.sigmoid(), g.tanh(), o.sigmoid()
     c_new = f * c_prev + i * g
     h_new = o * torch.tanh(c_new)
-    gates.copy_(torch.cat([i, f, g, o], dim=1))  # match GPU in-place contract
+    gates.copy_(torch.cat([i, f, g, o], dim=1))
     if out_h is not None:
         out_h.copy_(h_new)
         h_new = out_h
@@ -60,20 +48,7 @@ def _pointwise_fwd(gates: torch.Tensor, c_prev: torch.Tensor,
 def _pointwise_bwd(gates_act, c_prev, c_out, dh, dc_in,
                    out_dgates: torch.Tensor = None,
                    out_dc_prev: torch.Tensor = None):
-    B, H4 = gates_act.shape
-    H = H4 // 4
-    if gates_act.is_cuda:
-        dgates = out_dgates if out_dgates is not None else \
-            torch.empty_like(gates_act)
-        dc_prev = out_dc_prev if out_dc_prev is not None else torch.empty(
-            B, H, device=gates_act.device, dtype=torch.float32)
-        ret = _backend.lib().lstm_pointwise_bwd(
-            _c(gates_act.data_ptr()), _c(c_prev.data_ptr()), _c(c_out.data_ptr()),
-            _c(dh.data_ptr()), _c(dc_in.data_ptr()) if dc_in is not None else None,
-            _c(dgates.data_ptr()), _c(dc_prev.data_ptr()), B, H,
-            _backend.current_stream())
-        _backend.check(ret, "lstm_pointwise_bwd")
-        return dgates, dc_prev
+    """CPU oracle of one cell step's backward."""
     i, f, g, o = gates_act.chunk(4, dim=1)
     tc = torch.tanh(c_out)
     dc = dh * o * (1 - tc * tc)
@@ -94,12 +69,27 @@ def _pointwise_bwd(gates_act, c_prev, c_out, dh, dc_in,
     return dgates, dc_prev
 
 
+def _grad_epilogue(dgates_all, x, hs_in, w_ih):
+    """The four whole-sequence products every backward driver ends with."""
+    T, B, I = x.shape
+    dg2 = dgates_all.reshape(T * B, dgates_all.shape[-1])
+    dx = (dg2 @ w_ih).view(T, B, I)
+    dw_ih = dg2.t() @ x.reshape(T * B, I)
+    dw_hh = dg2.t() @ hs_in.reshape(T * B, hs_in.shape[-1])
+    db = dg2.sum(0)
+    return dx, dw_ih, dw_hh, db
+
+
 class _MaskedLSTMFn(torch.autograd.Function):
     """One LSTM layer unrolled over T with per-step done masking.
 
     x: [T,B,I]; notdone: [T,B,1]; h0,c0: [B,H]; weights nn.LSTM layout.
     Strategy: xW^T for all T hoisted to one GEMM; per step one GEMM + one
-    pointwise kernel.  Saves activated gates + cell states for backward.
+    fused cell kernel (csrc/lstm.hip) in each direction — the kernel also
+    does the done-masking, so no other launch sits in the loop.  Saves
+    activated gates + cell states for backward.  This is the driver that
+    runs inside the captured learner graph.  CPU tensors take the pure
+    torch branch (the oracle).
     """
 
     @staticmethod
@@ -108,17 +98,40 @@ class _MaskedLSTMFn(torch.autograd.Function):
         T, B, I = x.shape
         H = w_hh.shape[1]
         xg = torch.addmm(b_ih + b_hh, x.reshape(T * B, I), w_ih.t()).view(T, B, 4 * H)
-        h, c = h0.contiguous(), c0.contiguous()
         hs = torch.empty(T, B, H, device=x.device, dtype=x.dtype)
         cs_in = torch.empty(T, B, H, device=x.device, dtype=x.dtype)
         cs_out = torch.empty(T, B, H, device=x.device, dtype=x.dtype)
         hs_in = torch.empty(T, B, H, device=x.device, dtype=x.dtype)
-        gates_all = torch.empty(T, B, 4 * H, device=x.device, dtype=x.dtype)
         w_hh_t = w_hh.t()
+        ctx.H = H
+        if x.is_cuda:
+            lib = _backend.lib()
+            stream = _backend.current_stream()
+            nd = notdone.reshape(T, B).contiguous()
+            h0c, c0c = h0.contiguous(), c0.contiguous()
+            ret = lib.lstm_mask_rows(_cp(h0c), _cp(c0c), _cp(nd[0]),
+                                     _cp(hs_in[0]), _cp(cs_in[0]), B, H,
+                                     stream)
+            _backend.check(ret, "lstm_mask_rows")
+            for t in range(T):
+                # the recurrent product accumulates into the hoisted
+                # x-side preactivations: xg doubles as the saved gate
+                # buffer, no per-step copy
+                xg[t].addmm_(hs_in[t], w_hh_t)
+                last = t == T - 1
+                ret = lib.lstm_cell_fwd(
+                    _cp(xg[t]), _cp(cs_in[t]), _cp(hs[t]), _cp(cs_out[t]),
+                    None if last else _cp(nd[t + 1]),
+                    None if last else _cp(hs_in[t + 1]),
+                    None if last else _cp(cs_in[t + 1]), B, H, stream)
+                _backend.check(ret, "lstm_cell_fwd")
+            ctx.save_for_backward(x, nd, hs_in, cs_in, cs_out, xg, w_ih,
+                                  w_hh)
+            return hs, hs[T - 1].clone(), cs_out[T - 1].clone()
+        h, c = h0.contiguous(), c0.contiguous()
+        gates_all = torch.empty(T, B, 4 * H, device=x.device, dtype=x.dtype)
         for t in range(T):
             nd = notdone[t]
-            # out=-form writes land directly in the saved [T,...] buffers:
-            # 4 enqueues per step instead of 8 (the unroll is launch-bound)
             h = torch.mul(h, nd, out=hs_in[t])
             c = torch.mul(c, nd, out=cs_in[t])
             torch.addmm(xg[t], h, w_hh_t, out=gates_all[t])
@@ -126,7 +139,6 @@ class _MaskedLSTMFn(torch.autograd.Function):
                                   out_c=cs_out[t])
         ctx.save_for_backward(x, notdone, hs_in, cs_in, cs_out, gates_all,
                               w_ih, w_hh)
-        ctx.H = H
         # final h/c alias hs[T-1]/cs_out[T-1] after the out=-form loop;
         # clone so the Function's outputs don't share storage
         return hs, h.clone(), c.clone()
@@ -137,10 +149,31 @@ class _MaskedLSTMFn(torch.autograd.Function):
         (x, notdone, hs_in, cs_in, cs_out, gates_all, w_ih,
          w_hh) = ctx.saved_tensors
         T, B, I = x.shape
-        H = ctx.H
+        dgates_all = torch.empty_like(gates_all)
+        if x.is_cuda:
+            lib = _backend.lib()
+            stream = _backend.current_stream()
+            H = ctx.H
+            nd = notdone  # [T,B] contiguous, from forward
+            # locals keep the contiguous copies alive past the launches
+            d_hs_c = d_hs.contiguous()
+            d_hT_c = d_hT.contiguous()
+            dc_carry = d_cT.contiguous().clone()
+            g = torch.empty_like(dc_carry)  # raw dgates[t+1] @ w_hh
+            for t in range(T - 1, -1, -1):
+                last = t == T - 1
+                ret = lib.lstm_cell_bwd(
+                    _cp(gates_all[t]), _cp(cs_in[t]), _cp(cs_out[t]),
+                    _cp(d_hs_c[t]), _cp(d_hT_c) if last else _cp(g),
+                    None if last else _cp(nd[t + 1]), _cp(nd[t]),
+                    _cp(dc_carry), _cp(dgates_all[t]), B, H, stream)
+                _backend.check(ret, "lstm_cell_bwd")
+                torch.mm(dgates_all[t], w_hh, out=g)
+            dh0 = g.mul_(nd[0].unsqueeze(1))
+            dx, dw_ih, dw_hh, db = _grad_epilogue(dgates_all, x, hs_in, w_ih)
+            return dx, None, dh0, dc_carry, dw_ih, dw_hh, db, db
         dh_carry = d_hT.contiguous().clone()
         dc_carry = d_cT.contiguous().clone()
-        dgates_all = torch.empty_like(gates_all)
         dh_buf = torch.empty_like(dh_carry)
         dc_prev_buf = torch.empty_like(dc_carry)
         for t in range(T - 1, -1, -1):
@@ -152,21 +185,16 @@ class _MaskedLSTMFn(torch.autograd.Function):
             torch.mm(dgates, w_hh, out=dh_carry)
             dh_carry.mul_(nd)
             torch.mul(dc_prev, nd, out=dc_carry)
-        dg2 = dgates_all.reshape(T * B, 4 * H)
-        dx = (dg2 @ w_ih).view(T, B, I)
-        dw_ih = dg2.t() @ x.reshape(T * B, I)
-        dw_hh = dg2.t() @ hs_in.reshape(T * B, H)
-        db = dg2.sum(0)
+        dx, dw_ih, dw_hh, db = _grad_epilogue(dgates_all, x, hs_in, w_ih)
         return dx, None, dh_carry, dc_carry, dw_ih, dw_hh, db, db
 
 
 class _MaskedLSTMSeqFn(torch.autograd.Function):
     """One LSTM layer unrolled over T with the loop driven from C++
-    (csrc/lstm_seq.hip): per step one rocBLAS SGEMM + one fused kernel, all
-    enqueued natively — removes the ~20 ms/iter of Python launch overhead
-    the per-step path pays (profiles/README.md).  Numerics identical to
-    :class:`_MaskedLSTMFn`.  EXPERIMENTAL: enabled via SCALERL_LSTM_SEQ=1
-    until hardware-validated (its oracle test is test_lstm_seq*)."""
+    (csrc/lstm_seq.hip): per step one rocBLAS SGEMM + one fused cell kernel,
+    all enqueued natively — removes the ~20 ms/iter of Python launch
+    overhead the per-step path pays in eager mode (profiles/README.md).
+    Same kernels and numerics as :class:`_MaskedLSTMFn`; GPU only."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
@@ -177,23 +205,21 @@ class _MaskedLSTMSeqFn(torch.autograd.Function):
         dev = x.device
         xg = torch.addmm(b_ih + b_hh, x.reshape(T * B, I),
                          w_ih.t()).view(T, B, 4 * H).contiguous()
-        h = h0.contiguous().clone()
-        c = c0.contiguous().clone()
+        h0c, c0c = h0.contiguous(), c0.contiguous()
         hs = torch.empty(T, B, H, device=dev)
         hs_in = torch.empty(T, B, H, device=dev)
         cs_in = torch.empty(T, B, H, device=dev)
         cs_out = torch.empty(T, B, H, device=dev)
-        gemm_tmp = torch.empty(B, 4 * H, device=dev)
-        nd = notdone.reshape(T, B, 1)[:, :, 0].contiguous()
+        nd = notdone.reshape(T, B).contiguous()
         w_hh_c = w_hh.contiguous()
         ret = lib.masked_lstm_seq_fwd(
-            _cp(xg), _cp(w_hh_c), _cp(nd), _cp(h), _cp(c), _cp(hs),
-            _cp(hs_in), _cp(cs_in), _cp(cs_out), _cp(gemm_tmp), T, B, H,
+            _cp(xg), _cp(w_hh_c), _cp(nd), _cp(h0c), _cp(c0c), _cp(hs),
+            _cp(hs_in), _cp(cs_in), _cp(cs_out), T, B, H,
             _backend.current_stream())
         _backend.check(ret, "masked_lstm_seq_fwd")
         ctx.save_for_backward(x, nd, hs_in, cs_in, cs_out, xg, w_ih, w_hh_c)
         ctx.H = H
-        return hs, h, c
+        return hs, hs[T - 1].clone(), cs_out[T - 1].clone()
 
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
@@ -204,20 +230,18 @@ class _MaskedLSTMSeqFn(torch.autograd.Function):
         H = ctx.H
         dev = x.device
         dgates_all = torch.empty(T, B, 4 * H, device=dev)
-        dh_carry = d_hT.contiguous().clone()
+        # locals keep the contiguous copies alive past the launches
+        d_hs_c = d_hs.contiguous()
+        d_hT_c = d_hT.contiguous()
+        dh_carry = torch.empty(B, H, device=dev)
         dc_carry = d_cT.contiguous().clone()
-        dc_prev_tmp = torch.empty(B, H, device=dev)
         ret = lib.masked_lstm_seq_bwd(
-            _cp(gates_all), _cp(cs_in), _cp(cs_out),
-            _cp(d_hs.contiguous()), _cp(nd), _cp(w_hh), _cp(dgates_all),
-            _cp(dh_carry), _cp(dc_carry), _cp(dc_prev_tmp), T, B, H,
+            _cp(gates_all), _cp(cs_in), _cp(cs_out), _cp(d_hs_c),
+            _cp(d_hT_c), _cp(nd), _cp(w_hh), _cp(dgates_all),
+            _cp(dh_carry), _cp(dc_carry), T, B, H,
             _backend.current_stream())
         _backend.check(ret, "masked_lstm_seq_bwd")
-        dg2 = dgates_all.reshape(T * B, 4 * H)
-        dx = (dg2 @ w_ih).view(T, B, I)
-        dw_ih = dg2.t() @ x.reshape(T * B, I)
-        dw_hh = dg2.t() @ hs_in.reshape(T * B, H)
-        db = dg2.sum(0)
+        dx, dw_ih, dw_hh, db = _grad_epilogue(dgates_all, x, hs_in, w_ih)
         return dx, None, dh_carry, dc_carry, dw_ih, dw_hh, db, db
 
 

@@ -30,6 +30,9 @@ def main():
     p.add_argument("--warmup", type=int, default=10)
     p.add_argument("--use-lstm", type=int, default=1)
     p.add_argument("--dtype", type=str, default="bf16")
+    p.add_argument("--graph", type=int, default=0, choices=(0, 1),
+                   help="1: time the hipGraph-captured step the trainer "
+                        "replays (runtime/graphed.py) instead of the eager one")
     args = p.parse_args()
 
     dev = torch.device("cuda:0" if torch.cuda.is_available() else "cpu")
@@ -74,6 +77,24 @@ def main():
         opt.step(flat.flat_grad)
         pub.copy_(flat.flat, non_blocking=True)
         return total
+
+    if args.graph:
+        assert dev.type == "cuda", "--graph 1 needs a GPU"
+        from scalerl_amd.runtime.graphed import GraphedImpalaStep
+        example = dict(batch)
+        if args.use_lstm:
+            example["core_state"] = torch.stack(state)
+        # loss constants and flags as in step() above
+        graphed = GraphedImpalaStep(
+            model, flat.flat_grad, {}, example, bool(args.use_lstm),
+            torch.bfloat16 if autocast else None, True, 0.99)
+
+        def step():  # noqa: F811 — same work, fwd+bwd replayed from the graph
+            total, _ = graphed.run(example)
+            clip_grad_norm_(flat.flat_grad, 40.0)
+            opt.step(flat.flat_grad)
+            pub.copy_(flat.flat, non_blocking=True)
+            return total
 
     for _ in range(args.warmup):
         step()

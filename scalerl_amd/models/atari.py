@@ -11,12 +11,18 @@ MI355X design differences from the reference:
   GEMM + one fused HIP pointwise kernel per step) instead of a Python loop
   over nn.LSTM;
 - frames stay uint8 until the normalize-on-device divide;
+- on the GPU under bf16 autocast with gradients off (the batched inference
+  worker) the normalize and the three encoder convs run as one fused HIP
+  kernel (ops/encoder.py).  ``SCALERL_FUSED_ENCODER=0`` restores the
+  per-layer MIOpen forward; ``SCALERL_FUSED_ENCODER_TRAIN=1`` also takes the
+  fused forward where gradients are on (backward stays on MIOpen);
 - the conv/FC stack runs in bf16 under autocast on the learner (heads and
   LSTM stay fp32).
 """
 
 from __future__ import annotations
 
+import os
 from typing import Dict, Tuple
 
 import torch
@@ -24,11 +30,24 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..ops import MaskedLSTM, frame_cast
+from ..ops.encoder import fused_encoder
+
+# Fused encoder forward switches, read once at import; tests flip these
+# module-level flags to compare the paths in one process.
+# FUSED_ENCODER (default on): take the fused forward where gradients are off.
+# FUSED_ENCODER_TRAIN (default off): take it with gradients on as well.  Off
+# because the learner's clipped gradient at the bench shape then differs from
+# the unfused one by about its own norm (profiles/README.md, "Fused encoder
+# forward"); at N = 20 and N = 2048 the two bf16 paths are equally close to
+# fp32, and the cause at N = 20736 has not been found.
+FUSED_ENCODER = os.environ.get("SCALERL_FUSED_ENCODER", "1") != "0"
+FUSED_ENCODER_TRAIN = os.environ.get("SCALERL_FUSED_ENCODER_TRAIN", "0") == "1"
 
 
 class AtariNet(nn.Module):
     def __init__(self, observation_shape=(4, 84, 84), num_actions: int = 6,
-                 use_lstm: bool = True, native_conv: bool = None):
+                 use_lstm: bool = True, native_conv: bool = None,
+                 fused_encoder: bool = None):
         super().__init__()
         self.observation_shape = tuple(observation_shape)
         self.num_actions = num_actions
@@ -37,8 +56,16 @@ class AtariNet(nn.Module):
         # hardware-validated (r2); opt-in because MIOpen still wins the
         # per-op A/B (profiles/README.md; the panel/stride-decomposed v3
         # kernels queued for r3 close the gap).  Requires (4,84,84).
+        # fused_encoder: may encode() take the fused forward (ops/encoder.py)?
+        # None (the default) means yes, except that an explicit
+        # native_conv=False keeps its meaning "MIOpen convolutions only" and
+        # so rules the fused kernel out too; pass fused_encoder=True next to
+        # it to get the fused forward without the per-layer native kernels.
+        if fused_encoder is None:
+            fused_encoder = native_conv is not False
+        self.fused_encoder = (bool(fused_encoder) and
+                              tuple(observation_shape) == (4, 84, 84))
         if native_conv is None:
-            import os
             native_conv = bool(os.environ.get("SCALERL_NATIVE_CONV"))
         self.native_conv = native_conv and tuple(observation_shape) == (4, 84, 84)
 
@@ -69,8 +96,19 @@ class AtariNet(nn.Module):
             h = native_conv(2, h, self.conv2.weight, self.conv2.bias)
             h = native_conv(3, h, self.conv3.weight, self.conv3.bias)
             return F.relu(self.fc(torch.flatten(h, 1)))
-        if (x.is_cuda and x.dtype == torch.uint8 and
-                frame_cast.bf16_autocast_active()):
+        bf16_frames = (x.is_cuda and x.dtype == torch.uint8 and
+                       frame_cast.bf16_autocast_active())
+        if (bf16_frames and self.fused_encoder and FUSED_ENCODER and
+                (FUSED_ENCODER_TRAIN or not torch.is_grad_enabled()) and
+                x.is_contiguous() and x.data_ptr() % 16 == 0):
+            # normalize + conv1..3 (+bias, ReLU) forward in one kernel; it
+            # stages images with 16-byte loads, so an unaligned view of the
+            # frames takes the per-layer path below
+            h = fused_encoder(x, self.conv1.weight, self.conv1.bias,
+                              self.conv2.weight, self.conv2.bias,
+                              self.conv3.weight, self.conv3.bias)
+            return F.relu(self.fc(torch.flatten(h, 1)))
+        if bf16_frames:
             # autocast would cast the fp32 quotient to bf16 for conv1
             # anyway: one fused pass, same bits
             x = frame_cast.frame_to_bf16(x)

@@ -8,6 +8,7 @@ numerics oracles in ``tests/``.
 
 from ._backend import available as kernels_available
 from ._backend import build as build_kernels
+from .encoder import fused_encoder
 from .frame_cast import frame_to_bf16
 from .lstm import MaskedLSTM
 from .optim import FusedAdam, FusedRMSprop, clip_grad_norm_, fused_polyak_
@@ -26,5 +27,5 @@ __all__ = [
     "per_is_weights", "td_loss_reference", "VTraceReturns",
     "action_log_probs", "impala_loss", "impala_loss_reference",
     "vtrace_from_log_rhos", "vtrace_reference", "ppo_fused_loss",
-    "ppo_loss_reference", "frame_to_bf16",
+    "ppo_loss_reference", "frame_to_bf16", "fused_encoder",
 ]

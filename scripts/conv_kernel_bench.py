@@ -1,6 +1,11 @@
 #!/usr/bin/env python3
 """Per-op timing: native MFMA conv kernels vs torch/MIOpen at the bench
-shape (N = T+1 x B = 81*256 = 20736 images).  hipEvent-timed."""
+shape (N = T+1 x B = 81*256 = 20736 images).  hipEvent-timed.
+
+The first rows time the fused encoder forward (ops/encoder.py) against the
+frame cast + three MIOpen convs with ReLU under bf16 autocast, at the learner
+shape (N = 20736, activations saved) and at the inference round's
+(N = 6144, nothing saved).  ``--encoder-only`` stops after them."""
 import os
 import sys
 
@@ -10,6 +15,8 @@ os.environ.setdefault("MIOPEN_FIND_MODE", "1")
 import torch
 import torch.nn.functional as F
 
+from scalerl_amd.ops.encoder import atari_encoder_fwd
+from scalerl_amd.ops.frame_cast import frame_to_bf16
 from scalerl_amd.ops.conv import (atari_conv2_dgrad_v3, atari_conv_dgrad,
                                   atari_conv_fwd, atari_conv_fwd_v3,
                                   atari_conv_wgrad, atari_conv_wgrad_v3)
@@ -31,8 +38,40 @@ def timeit(fn, iters=10, warmup=3):
     return s.elapsed_time(e) / iters
 
 
+def encoder_rows():
+    """Fused encoder forward vs cast + 3 MIOpen convs, same process."""
+    g = torch.Generator().manual_seed(0)
+    wshapes = ((32, 4, 8, 8), (64, 32, 4, 4), (64, 64, 3, 3))
+    ws = [(torch.randn(s, generator=g) * 0.1).to(dev) for s in wshapes]
+    bs = [(torch.randn(s[0], generator=g) * 0.1).to(dev) for s in wshapes]
+    wb = [w.to(torch.bfloat16) for w in ws]
+    for n, save in ((20736, True), (6144, False)):
+        x = torch.randint(0, 256, (n, 4, 84, 84), dtype=torch.uint8,
+                          device=dev)
+
+        def fused():
+            return atari_encoder_fwd(x, wb[0], bs[0], wb[1], bs[1], wb[2],
+                                     bs[2], save)
+
+        def miopen():
+            with torch.no_grad(), \
+                    torch.autocast(device_type="cuda", dtype=torch.bfloat16):
+                h = frame_to_bf16(x)
+                for w, b, stride in zip(ws, bs, (4, 2, 1)):
+                    h = F.relu(F.conv2d(h, w, b, stride=stride))
+            return h
+
+        t_ref = timeit(miopen, iters=20, warmup=5)
+        t_fus = timeit(fused, iters=20, warmup=5)
+        print(f"encoder fwd N={n:5d} save={int(save)}: fused {t_fus:7.3f} ms"
+              f"  cast+miopen {t_ref:7.3f} ms  ratio {t_ref / t_fus:5.2f}x")
+
+
 def main():
     torch.manual_seed(0)
+    encoder_rows()
+    if "--encoder-only" in sys.argv[1:]:
+        return
     shapes = {
         1: ((4, 84, 84), (32, 4, 8, 8), 4, (32, 20, 20)),
         2: ((32, 20, 20), (64, 32, 4, 4), 2, (64, 9, 9)),

@@ -13,13 +13,10 @@
 //     come from global (L1-resident), dx staged through LDS for one
 //     coalesced vectorized writeback.
 //
-// Fragment maps as in conv_fwd.hip (validated by mfma_selftest).
+// Fragment maps for v_mfma_f32_16x16x32_bf16: mfma.h.
 
 #include "common.h"
-
-typedef __bf16 bf16_t;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef bf16_t bf16x8 __attribute__((ext_vector_type(8)));
+#include "mfma.h"
 
 // ---------------------------------------------------------------- wgrad --
 

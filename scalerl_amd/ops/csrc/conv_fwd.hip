@@ -21,19 +21,10 @@
 //    would otherwise scatter 2B stores across output planes);
 //  - grid = N (20736 at the bench batch) x 1-2 >> 256 CUs.
 //
-// Fragment maps for v_mfma_f32_16x16x32_bf16 (validated on-device by
-// mfma_selftest in conv_atari.hip):
-//   A (16x32): lane l, elem j -> row = l & 15, k = (l >> 4) * 8 + j
-//   B (32x16): lane l, elem j -> col = l & 15, k = (l >> 4) * 8 + j
-//   C/D:       lane l, reg r  -> col = l & 15, row = (l >> 4) * 4 + r
+// Fragment maps for v_mfma_f32_16x16x32_bf16: mfma.h.
 
 #include "common.h"
-
-typedef __bf16 bf16_t;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef bf16_t bf16x8 __attribute__((ext_vector_type(8)));
-typedef bf16_t bf16x4 __attribute__((ext_vector_type(4)));
-typedef bf16_t bf16x2 __attribute__((ext_vector_type(2)));
+#include "mfma.h"
 
 // ---------------------------------------------------------------- conv1 --
 // Block: 256 thr (4 waves), half an image's output rows (OYB=10 of 20).

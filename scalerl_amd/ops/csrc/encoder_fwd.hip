@@ -31,16 +31,12 @@
 //  - LDS: 32256 (image range / act2) + 25600 (act1) + 6272 (out3) = 64128 B,
 //    static, two workgroups per CU.
 //
-// Fragment maps for v_mfma_f32_16x16x32_bf16: header of conv_fwd.hip
-// (validated on-device by mfma_selftest).
+// Fragment maps for v_mfma_f32_16x16x32_bf16: mfma.h.
 
 #include "common.h"
 #include "frame_cast.h"
+#include "mfma.h"
 
-typedef __bf16 bf16_t;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef bf16_t bf16x8 __attribute__((ext_vector_type(8)));
-typedef bf16_t bf16x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {

@@ -14,25 +14,12 @@ are off (``models/atari.py``, ``FUSED_ENCODER_TRAIN``).
 
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
-from . import _backend, frame_cast
-
-_c = ctypes.c_void_p
+from . import frame_cast
+from ._backend import launch
 
 _W_SHAPES = ((32, 4, 8, 8), (64, 32, 4, 4), (64, 64, 3, 3))
-
-
-def _declare_encoder(lib):
-    if getattr(lib, "_encoder_declared", False):
-        return lib
-    c = ctypes
-    lib.atari_encoder_fwd.argtypes = [c.c_void_p] * 10 + [c.c_long, c.c_void_p]
-    lib.atari_encoder_fwd.restype = c.c_int
-    lib._encoder_declared = True
-    return lib
 
 
 @torch.no_grad()
@@ -43,16 +30,12 @@ def atari_encoder_fwd(x, w1, b1, w2, b2, w3, b3, save: bool):
     ``save``."""
     assert x.is_cuda and x.dtype == torch.uint8
     assert tuple(x.shape[1:]) == (4, 84, 84), x.shape
-    lib = _declare_encoder(_backend.lib())
     n = x.shape[0]
-    # every cast / contiguous temporary is bound to a local that outlives
-    # the launch (see the note in conv.atari_conv_wgrad)
     xc = x.contiguous()
     # the kernel stages images with 16-byte loads; an image is 1764 * 16
     # bytes, so only the base matters
     assert xc.data_ptr() % 16 == 0, "atari_encoder_fwd needs 16-byte aligned frames"
     ws = [w.to(torch.bfloat16).contiguous() for w in (w1, w2, w3)]
-    bs = [b.float().contiguous() for b in (b1, b2, b3)]
     for w, shape in zip(ws, _W_SHAPES):
         assert w.numel() == shape[0] * shape[1] * shape[2] * shape[3], w.shape
     dev = x.device
@@ -61,16 +44,9 @@ def atari_encoder_fwd(x, w1, b1, w2, b2, w3, b3, save: bool):
         out1 = torch.empty((n, 32, 20, 20), dtype=torch.bfloat16, device=dev)
         out2 = torch.empty((n, 64, 9, 9), dtype=torch.bfloat16, device=dev)
     out3 = torch.empty((n, 64, 7, 7), dtype=torch.bfloat16, device=dev)
-    ret = lib.atari_encoder_fwd(
-        _c(xc.data_ptr()),
-        _c(ws[0].data_ptr()), _c(bs[0].data_ptr()),
-        _c(ws[1].data_ptr()), _c(bs[1].data_ptr()),
-        _c(ws[2].data_ptr()), _c(bs[2].data_ptr()),
-        _c(out1.data_ptr()) if save else None,
-        _c(out2.data_ptr()) if save else None,
-        _c(out3.data_ptr()), n, _backend.current_stream())
-    _backend.check(ret, "atari_encoder_fwd")
-    del xc, ws, bs
+    launch("atari_encoder_fwd", xc,
+           ws[0], b1.float().contiguous(), ws[1], b2.float().contiguous(),
+           ws[2], b3.float().contiguous(), out1, out2, out3, n)
     return out1, out2, out3
 
 

@@ -8,13 +8,9 @@ the torch expression (the oracle).
 
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
-from . import _backend
-
-_c = ctypes.c_void_p
+from ._backend import launch
 
 
 def frame_to_bf16(x: torch.Tensor) -> torch.Tensor:
@@ -22,13 +18,8 @@ def frame_to_bf16(x: torch.Tensor) -> torch.Tensor:
     assert x.dtype == torch.uint8, "frame_to_bf16 takes uint8 frames"
     if not x.is_cuda:
         return (x.float() / 255.0).to(torch.bfloat16)
-    # bind the contiguous copy to a local that outlives the launch
-    xc = x.contiguous()
-    out = torch.empty(xc.shape, dtype=torch.bfloat16, device=xc.device)
-    ret = _backend.lib().frame_cast_u8_bf16(
-        _c(xc.data_ptr()), _c(out.data_ptr()), xc.numel(),
-        _backend.current_stream())
-    _backend.check(ret, "frame_cast_u8_bf16")
+    out = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device)
+    launch("frame_cast_u8_bf16", x.contiguous(), out, x.numel())
     return out
 
 

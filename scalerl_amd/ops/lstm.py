@@ -16,15 +16,12 @@ checkpoints interop with torch LSTMs.
 
 from __future__ import annotations
 
-import ctypes
 from typing import List, Tuple
 
 import torch
 import torch.nn as nn
 
-from . import _backend
-
-_c = ctypes.c_void_p
+from ._backend import launch
 
 
 def _pointwise_fwd(gates: torch.Tensor, c_prev: torch.Tensor,
@@ -105,26 +102,20 @@ class _MaskedLSTMFn(torch.autograd.Function):
         w_hh_t = w_hh.t()
         ctx.H = H
         if x.is_cuda:
-            lib = _backend.lib()
-            stream = _backend.current_stream()
             nd = notdone.reshape(T, B).contiguous()
-            h0c, c0c = h0.contiguous(), c0.contiguous()
-            ret = lib.lstm_mask_rows(_cp(h0c), _cp(c0c), _cp(nd[0]),
-                                     _cp(hs_in[0]), _cp(cs_in[0]), B, H,
-                                     stream)
-            _backend.check(ret, "lstm_mask_rows")
+            launch("lstm_mask_rows", h0.contiguous(), c0.contiguous(), nd[0],
+                   hs_in[0], cs_in[0], B, H)
             for t in range(T):
                 # the recurrent product accumulates into the hoisted
                 # x-side preactivations: xg doubles as the saved gate
                 # buffer, no per-step copy
                 xg[t].addmm_(hs_in[t], w_hh_t)
                 last = t == T - 1
-                ret = lib.lstm_cell_fwd(
-                    _cp(xg[t]), _cp(cs_in[t]), _cp(hs[t]), _cp(cs_out[t]),
-                    None if last else _cp(nd[t + 1]),
-                    None if last else _cp(hs_in[t + 1]),
-                    None if last else _cp(cs_in[t + 1]), B, H, stream)
-                _backend.check(ret, "lstm_cell_fwd")
+                launch("lstm_cell_fwd",
+                       xg[t], cs_in[t], hs[t], cs_out[t],
+                       None if last else nd[t + 1],
+                       None if last else hs_in[t + 1],
+                       None if last else cs_in[t + 1], B, H)
             ctx.save_for_backward(x, nd, hs_in, cs_in, cs_out, xg, w_ih,
                                   w_hh)
             return hs, hs[T - 1].clone(), cs_out[T - 1].clone()
@@ -151,23 +142,19 @@ class _MaskedLSTMFn(torch.autograd.Function):
         T, B, I = x.shape
         dgates_all = torch.empty_like(gates_all)
         if x.is_cuda:
-            lib = _backend.lib()
-            stream = _backend.current_stream()
             H = ctx.H
             nd = notdone  # [T,B] contiguous, from forward
-            # locals keep the contiguous copies alive past the launches
             d_hs_c = d_hs.contiguous()
             d_hT_c = d_hT.contiguous()
             dc_carry = d_cT.contiguous().clone()
             g = torch.empty_like(dc_carry)  # raw dgates[t+1] @ w_hh
             for t in range(T - 1, -1, -1):
                 last = t == T - 1
-                ret = lib.lstm_cell_bwd(
-                    _cp(gates_all[t]), _cp(cs_in[t]), _cp(cs_out[t]),
-                    _cp(d_hs_c[t]), _cp(d_hT_c) if last else _cp(g),
-                    None if last else _cp(nd[t + 1]), _cp(nd[t]),
-                    _cp(dc_carry), _cp(dgates_all[t]), B, H, stream)
-                _backend.check(ret, "lstm_cell_bwd")
+                launch("lstm_cell_bwd",
+                       gates_all[t], cs_in[t], cs_out[t],
+                       d_hs_c[t], d_hT_c if last else g,
+                       None if last else nd[t + 1], nd[t],
+                       dc_carry, dgates_all[t], B, H)
                 torch.mm(dgates_all[t], w_hh, out=g)
             dh0 = g.mul_(nd[0].unsqueeze(1))
             dx, dw_ih, dw_hh, db = _grad_epilogue(dgates_all, x, hs_in, w_ih)
@@ -199,24 +186,19 @@ class _MaskedLSTMSeqFn(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, x, notdone, h0, c0, w_ih, w_hh, b_ih, b_hh):
-        lib = _backend.lib()
         T, B, I = x.shape
         H = w_hh.shape[1]
         dev = x.device
         xg = torch.addmm(b_ih + b_hh, x.reshape(T * B, I),
                          w_ih.t()).view(T, B, 4 * H).contiguous()
-        h0c, c0c = h0.contiguous(), c0.contiguous()
         hs = torch.empty(T, B, H, device=dev)
         hs_in = torch.empty(T, B, H, device=dev)
         cs_in = torch.empty(T, B, H, device=dev)
         cs_out = torch.empty(T, B, H, device=dev)
         nd = notdone.reshape(T, B).contiguous()
         w_hh_c = w_hh.contiguous()
-        ret = lib.masked_lstm_seq_fwd(
-            _cp(xg), _cp(w_hh_c), _cp(nd), _cp(h0c), _cp(c0c), _cp(hs),
-            _cp(hs_in), _cp(cs_in), _cp(cs_out), T, B, H,
-            _backend.current_stream())
-        _backend.check(ret, "masked_lstm_seq_fwd")
+        launch("masked_lstm_seq_fwd", xg, w_hh_c, nd, h0.contiguous(),
+               c0.contiguous(), hs, hs_in, cs_in, cs_out, T, B, H)
         ctx.save_for_backward(x, nd, hs_in, cs_in, cs_out, xg, w_ih, w_hh_c)
         ctx.H = H
         return hs, hs[T - 1].clone(), cs_out[T - 1].clone()
@@ -224,32 +206,20 @@ class _MaskedLSTMSeqFn(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, d_hs, d_hT, d_cT):
-        lib = _backend.lib()
         x, nd, hs_in, cs_in, cs_out, gates_all, w_ih, w_hh = ctx.saved_tensors
         T, B, I = x.shape
         H = ctx.H
         dev = x.device
         dgates_all = torch.empty(T, B, 4 * H, device=dev)
-        # locals keep the contiguous copies alive past the launches
-        d_hs_c = d_hs.contiguous()
-        d_hT_c = d_hT.contiguous()
         dh_carry = torch.empty(B, H, device=dev)
         dc_carry = d_cT.contiguous().clone()
-        ret = lib.masked_lstm_seq_bwd(
-            _cp(gates_all), _cp(cs_in), _cp(cs_out), _cp(d_hs_c),
-            _cp(d_hT_c), _cp(nd), _cp(w_hh), _cp(dgates_all),
-            _cp(dh_carry), _cp(dc_carry), T, B, H,
-            _backend.current_stream())
-        _backend.check(ret, "masked_lstm_seq_bwd")
+        launch("masked_lstm_seq_bwd", gates_all, cs_in, cs_out,
+               d_hs.contiguous(), d_hT.contiguous(), nd, w_hh, dgates_all,
+               dh_carry, dc_carry, T, B, H)
         dx, dw_ih, dw_hh, db = _grad_epilogue(dgates_all, x, hs_in, w_ih)
         return dx, None, dh_carry, dc_carry, dw_ih, dw_hh, db, db
 
 
-def _cp(t: torch.Tensor):
-    return _c(t.data_ptr())
-
-
-_c = ctypes.c_void_p
 _USE_SEQ = None
 
 

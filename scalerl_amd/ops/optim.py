@@ -9,14 +9,11 @@ share_optim.py:65-122 — so checkpoints interop).
 
 from __future__ import annotations
 
-import ctypes
 from typing import Optional
 
 import torch
 
-from . import _backend
-
-_c = ctypes.c_void_p
+from ._backend import launch
 
 
 class FusedRMSprop:
@@ -36,13 +33,9 @@ class FusedRMSprop:
     def step(self, grad: torch.Tensor, lr: Optional[float] = None) -> None:
         lr = self.lr if lr is None else lr
         if self.param.is_cuda:
-            ret = _backend.lib().fused_rmsprop(
-                _c(self.param.data_ptr()), _c(grad.data_ptr()),
-                _c(self.square_avg.data_ptr()),
-                _c(self.momentum_buf.data_ptr()) if self.momentum_buf is not None else None,
-                self.param.numel(), lr, self.alpha, self.eps, self.momentum,
-                self.weight_decay, _backend.current_stream())
-            _backend.check(ret, "fused_rmsprop")
+            launch("fused_rmsprop", self.param, grad, self.square_avg,
+                   self.momentum_buf, self.param.numel(), lr, self.alpha,
+                   self.eps, self.momentum, self.weight_decay)
             return
         g = grad if self.weight_decay == 0 else grad + self.weight_decay * self.param
         self.square_avg.mul_(self.alpha).addcmul_(g, g, value=1 - self.alpha)
@@ -84,12 +77,9 @@ class FusedAdam:
         self.step_count += 1
         b1, b2 = self.betas
         if self.param.is_cuda:
-            ret = _backend.lib().fused_adam(
-                _c(self.param.data_ptr()), _c(grad.data_ptr()),
-                _c(self.exp_avg.data_ptr()), _c(self.exp_avg_sq.data_ptr()),
-                self.param.numel(), lr, b1, b2, self.eps, self.weight_decay,
-                self.step_count, _backend.current_stream())
-            _backend.check(ret, "fused_adam")
+            launch("fused_adam", self.param, grad, self.exp_avg,
+                   self.exp_avg_sq, self.param.numel(), lr, b1, b2, self.eps,
+                   self.weight_decay, self.step_count)
             return
         g = grad if self.weight_decay == 0 else grad + self.weight_decay * self.param
         self.exp_avg.mul_(b1).add_(g, alpha=1 - b1)
@@ -115,10 +105,7 @@ class FusedAdam:
 def fused_polyak_(dst: torch.Tensor, src: torch.Tensor, tau: float) -> None:
     """dst ← τ·src + (1−τ)·dst over flat buffers."""
     if dst.is_cuda:
-        ret = _backend.lib().fused_polyak(
-            _c(dst.data_ptr()), _c(src.data_ptr()), dst.numel(), tau,
-            _backend.current_stream())
-        _backend.check(ret, "fused_polyak")
+        launch("fused_polyak", dst, src, dst.numel(), tau)
     else:
         dst.lerp_(src, tau)
 
@@ -137,10 +124,7 @@ def clip_grad_norm_(grad: torch.Tensor, max_norm: float,
             scratch = torch.zeros(1, device=grad.device, dtype=torch.float32)
         else:
             scratch.zero_()
-        ret = _backend.lib().grad_clip_by_norm(
-            _c(grad.data_ptr()), grad.numel(), _c(scratch.data_ptr()),
-            max_norm, _backend.current_stream())
-        _backend.check(ret, "grad_clip_by_norm")
+        launch("grad_clip_by_norm", grad, grad.numel(), scratch, max_norm)
         return scratch
     norm = grad.norm()
     if norm > max_norm:

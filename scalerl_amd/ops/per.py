@@ -7,14 +7,11 @@ Reference: data/segment_tree.py:7-197, replay_buffer.py:276-381.
 
 from __future__ import annotations
 
-import ctypes
 from typing import Tuple
 
 import torch
 
-from . import _backend
-
-_c = ctypes.c_void_p
+from ._backend import launch
 
 
 def _next_pow2(n: int) -> int:
@@ -54,10 +51,7 @@ class SumTree:
             max_idx = int(idx.max()) + 1
         self.size = max(self.size, max_idx)
         if self.tree.is_cuda:
-            ret = _backend.lib().per_update(
-                _c(self.tree.data_ptr()), self.M, _c(idx.data_ptr()),
-                _c(prio.data_ptr()), idx.numel(), _backend.current_stream())
-            _backend.check(ret, "per_update")
+            launch("per_update", self.tree, self.M, idx, prio, idx.numel())
             return
         for k in range(idx.numel()):
             node = self.M + int(idx[k])
@@ -73,11 +67,8 @@ class SumTree:
         if self.tree.is_cuda:
             idx = torch.empty(batch, dtype=torch.long, device=self.device)
             prio = torch.empty(batch, dtype=torch.float32, device=self.device)
-            ret = _backend.lib().per_sample(
-                _c(self.tree.data_ptr()), self.M, self.size, _c(u.data_ptr()),
-                batch, _c(idx.data_ptr()), _c(prio.data_ptr()),
-                _backend.current_stream())
-            _backend.check(ret, "per_sample")
+            launch("per_sample", self.tree, self.M, self.size, u, batch, idx,
+                   prio)
             return idx, prio
         total = float(self.tree[1])
         idx = torch.empty(batch, dtype=torch.long)
@@ -101,10 +92,8 @@ class SumTree:
         """Min priority among live leaves (device scalar)."""
         if self.tree.is_cuda:
             self._min_bits.fill_(0x7f7fffff)  # +FLT_MAX bits
-            ret = _backend.lib().per_leaf_min(
-                _c(self.tree.data_ptr()), self.M, self.size,
-                _c(self._min_bits.data_ptr()), _backend.current_stream())
-            _backend.check(ret, "per_leaf_min")
+            launch("per_leaf_min", self.tree, self.M, self.size,
+                   self._min_bits)
             return self._min_bits.view(torch.float32)[0]
         return self.tree[self.M:self.M + self.size].min()
 

@@ -2,15 +2,12 @@
 
 from __future__ import annotations
 
-import ctypes
 from typing import Tuple
 
 import torch
 import torch.nn.functional as F
 
-from . import _backend
-
-_c = ctypes.c_void_p
+from ._backend import launch
 
 
 def ppo_loss_reference(logits, actions, old_logp, adv, returns, values,
@@ -30,43 +27,21 @@ def ppo_loss_reference(logits, actions, old_logp, adv, returns, values,
     return total, pg.detach(), v_loss.detach(), ent.detach()
 
 
-def _declare(lib):
-    if getattr(lib, "_ppo_declared", False):
-        return lib
-    c = ctypes
-    lib.ppo_fused_loss.argtypes = [c.c_void_p] * 6 + [c.c_float] * 3 + \
-        [c.c_long, c.c_long] + [c.c_void_p] * 4
-    lib.ppo_fused_loss.restype = c.c_int
-    lib._ppo_declared = True
-    return lib
-
-
 class _PPOFusedLossFn(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, logits, values, actions, old_logp, adv, returns,
                 clip_eps, vcoef, ecoef):
-        lib = _declare(_backend.lib())
         N, A = logits.shape
         lg = logits.contiguous()
         vals = values.contiguous()
         grad_logits = torch.empty_like(lg)
         grad_values = torch.empty_like(vals)
         loss_out = torch.zeros(3, device=lg.device)
-        # locals keep the cast temps alive past the launch (see ops/td.py)
-        act = actions.contiguous().long()
-        olp = old_logp.contiguous().float()
-        advc = adv.contiguous().float()
-        retc = returns.contiguous().float()
-        ret = lib.ppo_fused_loss(
-            _c(lg.data_ptr()), _c(act.data_ptr()),
-            _c(olp.data_ptr()),
-            _c(advc.data_ptr()),
-            _c(retc.data_ptr()),
-            _c(vals.data_ptr()), clip_eps, vcoef, ecoef, N, A,
-            _c(grad_logits.data_ptr()), _c(grad_values.data_ptr()),
-            _c(loss_out.data_ptr()), _backend.current_stream())
-        _backend.check(ret, "ppo_fused_loss")
+        launch("ppo_fused_loss", lg, actions.contiguous().long(),
+               old_logp.contiguous().float(), adv.contiguous().float(),
+               returns.contiguous().float(), vals, clip_eps, vcoef, ecoef,
+               N, A, grad_logits, grad_values, loss_out)
         ctx.save_for_backward(grad_logits, grad_values)
         ctx.mark_non_differentiable(loss_out)
         total = loss_out[0] + vcoef * loss_out[1] - ecoef * loss_out[2]

@@ -7,11 +7,9 @@ n-step — replay_buffer.py:230-273.
 
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
-from . import _backend
+from ._backend import launch
 
 
 @torch.no_grad()
@@ -34,17 +32,11 @@ def gae(rewards, values, bootstrap_value, discounts, lam: float = 0.95):
         return gae_reference(rewards, values, bootstrap_value, discounts, lam)
     T, B = rewards.shape
     r = rewards.contiguous().float()
-    v = values.contiguous().float()
-    bv = bootstrap_value.contiguous().float()
-    d = discounts.contiguous().float()
     advantages = torch.empty_like(r)
     returns = torch.empty_like(r)
-    c = ctypes.c_void_p
-    ret = _backend.lib().gae_scan(
-        c(r.data_ptr()), c(v.data_ptr()), c(bv.data_ptr()), c(d.data_ptr()),
-        lam, T, B, c(advantages.data_ptr()), c(returns.data_ptr()),
-        _backend.current_stream())
-    _backend.check(ret, "gae_scan")
+    launch("gae_scan", r, values.contiguous().float(),
+           bootstrap_value.contiguous().float(),
+           discounts.contiguous().float(), lam, T, B, advantages, returns)
     return advantages, returns
 
 
@@ -62,16 +54,10 @@ def discounted_returns(rewards, discounts, bootstrap_value=None):
         return out
     T, B = rewards.shape
     r = rewards.contiguous().float()
-    d = discounts.contiguous().float()
     out = torch.empty_like(r)
-    c = ctypes.c_void_p
-    bv = (bootstrap_value.contiguous().float()
-          if bootstrap_value is not None else None)
-    ret = _backend.lib().discounted_returns(
-        c(r.data_ptr()), c(d.data_ptr()),
-        c(bv.data_ptr()) if bv is not None else None,
-        T, B, c(out.data_ptr()), _backend.current_stream())
-    _backend.check(ret, "discounted_returns")
+    launch("discounted_returns", r, discounts.contiguous().float(),
+           bootstrap_value.contiguous().float()
+           if bootstrap_value is not None else None, T, B, out)
     return out
 
 
@@ -103,14 +89,9 @@ def nstep_fold(rewards, dones, gamma: float, n: int):
         return fr, fd, su
     T, B = rewards.shape
     r = rewards.contiguous().float()
-    d = dones.contiguous().float()
     fr = torch.empty_like(r)
     fd = torch.empty_like(r)
     su = torch.empty(T, B, dtype=torch.int32, device=r.device)
-    c = ctypes.c_void_p
-    ret = _backend.lib().nstep_fold(
-        c(r.data_ptr()), c(d.data_ptr()), gamma, n, T, B,
-        c(fr.data_ptr()), c(fd.data_ptr()), c(su.data_ptr()),
-        _backend.current_stream())
-    _backend.check(ret, "nstep_fold")
+    launch("nstep_fold", r, dones.contiguous().float(), gamma, n, T, B,
+           fr, fd, su)
     return fr, fd, su

@@ -7,14 +7,11 @@ apex/worker.py:134-161 (IS weights, priority update).
 
 from __future__ import annotations
 
-import ctypes
 from typing import Tuple
 
 import torch
 
-from . import _backend
-
-_c = ctypes.c_void_p
+from ._backend import launch
 
 
 def td_loss_reference(q, q_next_online, q_next_target, actions, rewards,
@@ -56,30 +53,14 @@ class _FusedTDLossFn(torch.autograd.Function):
         grad_q = torch.zeros_like(qc)
         td_abs = torch.empty(B, device=q.device, dtype=torch.float32)
         loss_out = torch.zeros(1, device=q.device, dtype=torch.float32)
-        # bind every cast/contiguous temp to a local that outlives the
-        # launch: a data_ptr() taken from an unreferenced temp is freed
-        # before the ctypes call runs, and the next argument's allocation
-        # can reuse+overwrite the block (the r2 dgrad corruption)
-        qno = (q_next_online.contiguous().float()
-               if q_next_online is not None else None)
-        qnt = q_next_target.contiguous().float()
-        act = actions.contiguous().long()
-        rew = rewards.contiguous().float()
-        dis = discounts.contiguous().float()
-        ret = _backend.lib().fused_td_loss(
-            _c(qc.data_ptr()),
-            _c(qno.data_ptr()) if qno is not None else None,
-            _c(qnt.data_ptr()),
-            _c(act.data_ptr()),
-            _c(rew.data_ptr()),
-            _c(dis.data_ptr()),
-            _c(prios.data_ptr()) if prios is not None else None,
-            _c(p_total.data_ptr()) if p_total is not None else None,
-            _c(p_min.data_ptr()) if p_min is not None else None,
-            float(beta), int(replay_size), B, A, int(huber),
-            float(huber_delta), _c(grad_q.data_ptr()), _c(td_abs.data_ptr()),
-            _c(loss_out.data_ptr()), _backend.current_stream())
-        _backend.check(ret, "fused_td_loss")
+        launch("fused_td_loss", qc,
+               q_next_online.contiguous().float()
+               if q_next_online is not None else None,
+               q_next_target.contiguous().float(),
+               actions.contiguous().long(), rewards.contiguous().float(),
+               discounts.contiguous().float(), prios, p_total, p_min,
+               float(beta), int(replay_size), B, A, int(huber),
+               float(huber_delta), grad_q, td_abs, loss_out)
         ctx.save_for_backward(grad_q)
         ctx.mark_non_differentiable(td_abs)
         return loss_out[0], td_abs

@@ -10,11 +10,10 @@ launch.
 from __future__ import annotations
 
 import collections
-import ctypes
 import torch
 import torch.nn.functional as F
 
-from . import _backend
+from ._backend import launch
 
 VTraceReturns = collections.namedtuple("VTraceReturns", ["vs", "pg_advantages"])
 
@@ -64,12 +63,8 @@ def vtrace_from_log_rhos(log_rhos, discounts, rewards, values, bootstrap_value,
             (log_rhos, discounts, rewards, values, bootstrap_value)]
     vs = torch.empty_like(args[0])
     pg_adv = torch.empty_like(args[0])
-    ret = _backend.lib().vtrace_from_log_rhos(
-        *[ctypes.c_void_p(a.data_ptr()) for a in args],
-        clip_rho_threshold, clip_c_threshold, clip_pg_rho_threshold,
-        T, B, ctypes.c_void_p(vs.data_ptr()), ctypes.c_void_p(pg_adv.data_ptr()),
-        _backend.current_stream())
-    _backend.check(ret, "vtrace_from_log_rhos")
+    launch("vtrace_from_log_rhos", *args, clip_rho_threshold,
+           clip_c_threshold, clip_pg_rho_threshold, T, B, vs, pg_adv)
     return VTraceReturns(vs=vs, pg_advantages=pg_adv)
 
 
@@ -107,29 +102,16 @@ class _ImpalaFusedLossFn(torch.autograd.Function):
         T, B, A = target_logits.shape
         tl = target_logits.contiguous().float()
         vals = values.contiguous().float()
-        bl = behavior_logits.contiguous().float()
-        acts = actions.contiguous().long()
         grad_logits = torch.empty_like(tl)
         grad_values = torch.empty_like(vals)
         loss_out = torch.zeros(3, device=tl.device, dtype=torch.float32)
         vs_out = torch.empty_like(vals) if want_vs else None
-        c = ctypes.c_void_p
-        # locals keep the cast temps alive past the launch (see ops/td.py)
-        rew = rewards.contiguous().float()
-        dis = discounts.contiguous().float()
-        bv = bootstrap_value.contiguous().float()
-        ret = _backend.lib().impala_fused_loss(
-            c(bl.data_ptr()), c(tl.data_ptr()), c(acts.data_ptr()),
-            c(rew.data_ptr()),
-            c(dis.data_ptr()),
-            c(vals.data_ptr()),
-            c(bv.data_ptr()),
-            clip_rho, clip_c, clip_pg_rho, baseline_cost, entropy_cost,
-            T, B, A, c(grad_logits.data_ptr()), c(grad_values.data_ptr()),
-            c(loss_out.data_ptr()),
-            c(vs_out.data_ptr()) if vs_out is not None else None,
-            _backend.current_stream())
-        _backend.check(ret, "impala_fused_loss")
+        launch("impala_fused_loss", behavior_logits.contiguous().float(), tl,
+               actions.contiguous().long(), rewards.contiguous().float(),
+               discounts.contiguous().float(), vals,
+               bootstrap_value.contiguous().float(),
+               clip_rho, clip_c, clip_pg_rho, baseline_cost, entropy_cost,
+               T, B, A, grad_logits, grad_values, loss_out, vs_out)
         ctx.save_for_backward(grad_logits, grad_values)
         total = (loss_out[0] + baseline_cost * loss_out[1]
                  + entropy_cost * loss_out[2])

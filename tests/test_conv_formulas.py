@@ -2,8 +2,9 @@
 
 The MFMA fragment mapping is hardware-validated (test_conv_experimental);
 these tests validate the OTHER half of the backward kernels — the
-implicit-GEMM index decode and validity masks in csrc/conv_atari.hip —
-by executing the exact same formulas in Python on small shapes.  A bug in
+implicit-GEMM index decode and validity masks of the v2 kernels in
+csrc/conv_fwd.hip (convN_fwd_v2) and csrc/conv_bwd.hip (convN_wgrad_v2,
+convN_dgrad_v2) — by executing the exact same formulas in Python on small shapes.  A bug in
 the kernels' gather math would show here without needing a GPU."""
 
 import numpy as np
@@ -22,7 +23,7 @@ def _out_hw(ih, iw, kh, kw, s):
 
 def emu_fwd(x, w, stride):
     """The fwd kernel's formula: out[p, k_out] = sum_k A[p,k]*B[k,k_out]
-    with A gathered as in conv_fwd_kernel."""
+    with A gathered as in the convN_fwd_v2 kernels."""
     N, C, IH, IW = x.shape
     K, _, KH, KW = w.shape
     OH, OW = _out_hw(IH, IW, KH, KW, stride)
@@ -42,7 +43,7 @@ def emu_fwd(x, w, stride):
 
 
 def emu_wgrad(x, dy, stride, kshape):
-    """conv_wgrad_kernel's formula."""
+    """convN_wgrad_v2's formula."""
     K, C, KH, KW = kshape
     N, _, IH, IW = x.shape
     OH, OW = _out_hw(IH, IW, KH, KW, stride)
@@ -60,7 +61,7 @@ def emu_wgrad(x, dy, stride, kshape):
 
 
 def emu_dgrad(dy, w, stride, in_shape):
-    """conv_dgrad_kernel's formula incl. the stride-validity mask."""
+    """convN_dgrad_v2's formula incl. the stride-validity mask."""
     C, IH, IW = in_shape
     K, _, KH, KW = w.shape
     N = dy.shape[0]

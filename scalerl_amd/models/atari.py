@@ -233,15 +233,18 @@ class CategoricalAtariQNet(nn.Module):
         from .noisy import reset_noise
         reset_noise(self)
 
-    def dist(self, x: torch.Tensor) -> torch.Tensor:
-        """→ log-probabilities [B, A, atoms]."""
+    def logits(self, x: torch.Tensor) -> torch.Tensor:
+        """→ raw atom logits [B, A, atoms]."""
         x = x.float() / 255.0
         x = F.relu(self.conv1(x))
         x = F.relu(self.conv2(x))
         x = F.relu(self.conv3(x))
         h = F.relu(self.fc(torch.flatten(x, 1)))
-        logits = self.head(h).view(-1, self.num_actions, self.num_atoms)
-        return F.log_softmax(logits, dim=-1)
+        return self.head(h).view(-1, self.num_actions, self.num_atoms)
+
+    def dist(self, x: torch.Tensor) -> torch.Tensor:
+        """→ log-probabilities [B, A, atoms]."""
+        return F.log_softmax(self.logits(x), dim=-1)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """Expected Q-values [B, A]."""

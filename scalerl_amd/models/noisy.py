@@ -79,11 +79,14 @@ class CategoricalQNet(nn.Module):
         self.v_min, self.v_max = v_min, v_max
         self.delta_z = (v_max - v_min) / (num_atoms - 1)
 
+    def logits(self, obs: torch.Tensor) -> torch.Tensor:
+        """→ raw atom logits [B, A, atoms]."""
+        h = self.body(obs)
+        return self.head(h).view(-1, self.action_dim, self.num_atoms)
+
     def dist(self, obs: torch.Tensor) -> torch.Tensor:
         """→ log-probabilities [B, A, atoms]."""
-        h = self.body(obs)
-        logits = self.head(h).view(-1, self.action_dim, self.num_atoms)
-        return F.log_softmax(logits, dim=-1)
+        return F.log_softmax(self.logits(obs), dim=-1)
 
     def forward(self, obs: torch.Tensor) -> torch.Tensor:
         """Expected Q-values [B, A]."""
@@ -92,29 +95,30 @@ class CategoricalQNet(nn.Module):
 
 def c51_loss(net: CategoricalQNet, target_net: CategoricalQNet, obs, actions,
              rewards, discounts, next_obs, double: bool = True,
-             weights=None):
+             weights=None, *, prios=None, p_total=None, p_min=None,
+             beta: float = 0.4, replay_size: int = 0):
     """Categorical projection TD loss (Bellemare et al. 2017, alg. 1).
 
-    Returns (loss scalar, |TD|-style priorities = per-sample KL)."""
-    B = obs.shape[0]
+    Returns (loss scalar, |TD|-style priorities = per-sample KL).
+
+    The nets only produce logits; the loss itself is
+    :func:`scalerl_amd.ops.fused_c51_loss` — one HIP kernel on the GPU, the
+    composed reference on the CPU.  PER importance-sampling weights come
+    from the raw ``prios``/``p_total``/``p_min`` (computed in-kernel on the
+    GPU); explicit ``weights`` instead select the composed reference on
+    either device."""
+    from ..ops.td import c51_loss_reference, fused_c51_loss
+    if weights is not None and prios is not None:
+        raise ValueError("pass either weights or prios, not both")
     with torch.no_grad():
-        next_q = (net if double else target_net)(next_obs)
-        astar = next_q.argmax(dim=1)
-        next_dist = target_net.dist(next_obs).exp()[
-            torch.arange(B), astar]                       # [B, atoms]
-        tz = (rewards.unsqueeze(1)
-              + discounts.unsqueeze(1) * net.support.unsqueeze(0))
-        tz = tz.clamp(net.v_min, net.v_max)
-        b = (tz - net.v_min) / net.delta_z
-        lo = b.floor().long().clamp(0, net.num_atoms - 1)
-        hi = b.ceil().long().clamp(0, net.num_atoms - 1)
-        proj = torch.zeros_like(next_dist)
-        # distribute mass to the two neighbouring atoms
-        lo_w = (hi.float() - b).where(hi != lo, torch.ones_like(b))
-        hi_w = (b - lo.float())
-        proj.scatter_add_(1, lo, next_dist * lo_w)
-        proj.scatter_add_(1, hi, next_dist * hi_w)
-    log_p = net.dist(obs)[torch.arange(B), actions]       # [B, atoms]
-    kl = -(proj * log_p).sum(dim=1)
-    loss = (kl * weights).mean() if weights is not None else kl.mean()
-    return loss, kl.detach()
+        next_online = net.logits(next_obs) if double else None
+        next_target = target_net.logits(next_obs)
+    logits = net.logits(obs)
+    if weights is not None:
+        return c51_loss_reference(logits, next_online, next_target, actions,
+                                  rewards, discounts, net.v_min, net.v_max,
+                                  weights)
+    return fused_c51_loss(logits, next_online, next_target, actions, rewards,
+                          discounts, net.v_min, net.v_max, prios=prios,
+                          p_total=p_total, p_min=p_min, beta=beta,
+                          replay_size=replay_size)

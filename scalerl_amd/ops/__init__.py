@@ -14,7 +14,8 @@ from .lstm import MaskedLSTM
 from .optim import FusedAdam, FusedRMSprop, clip_grad_norm_, fused_polyak_
 from .per import SumTree
 from .scans import discounted_returns, gae, nstep_fold
-from .td import fused_td_loss, per_is_weights, td_loss_reference
+from .td import (c51_loss_reference, fused_c51_loss, fused_td_loss,
+                 per_is_weights, td_loss_reference)
 from .ppo import ppo_fused_loss, ppo_loss_reference
 from .vtrace import (VTraceReturns, action_log_probs, impala_loss,
                      impala_loss_reference, vtrace_from_log_rhos,
@@ -27,5 +28,6 @@ __all__ = [
     "per_is_weights", "td_loss_reference", "VTraceReturns",
     "action_log_probs", "impala_loss", "impala_loss_reference",
     "vtrace_from_log_rhos", "vtrace_reference", "ppo_fused_loss",
-    "ppo_loss_reference", "frame_to_bf16", "fused_encoder",
+    "ppo_loss_reference", "frame_to_bf16", "fused_encoder", "fused_c51_loss",
+    "c51_loss_reference",
 ]

@@ -78,7 +78,7 @@ _SIGNATURES = {
     "fused_polyak": "f32 f32 long float",
     "grad_clip_by_norm": "f32 long f32 float",
     "fused_td_loss": "f32 f32? f32 i64 f32 f32 f32? f32? f32? float long long"
-                     " long int float f32 f32 f32",
+                     " long int float long float float f32 f32 f32",
     "ppo_fused_loss": "f32 i64 f32 f32 f32 f32 float float float long long"
                       " f32 f32 f32",
     "per_update": "f32 long i64 f32 long",
@@ -265,6 +265,8 @@ def launch(name: str, *args) -> None:
             hint = " (action-space size exceeds kernel MAX_A)"
         elif ret == -3:
             hint = " (rollout length exceeds LDS budget)"
+        elif ret == -4:
+            hint = " (atom count outside the C51 kernel's 2..1024)"
         raise RuntimeError(
             f"HIP kernel {name} failed with code {ret}{hint}; "
             f"device={torch.cuda.get_device_name()}")

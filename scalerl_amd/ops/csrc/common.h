@@ -24,6 +24,20 @@ __device__ __forceinline__ float wave_reduce_sum(float v) {
   return v;  // valid in lane 0 of the wave
 }
 
+// Wave-wide sum / max, the same value in every lane: the shfl_down tree of
+// wave_reduce_sum (one fixed order, so bitwise reproducible), then lane 0's
+// result broadcast.
+__device__ __forceinline__ float wave_all_sum(float v) {
+  return __shfl(wave_reduce_sum(v), 0, WAVE);
+}
+
+__device__ __forceinline__ float wave_all_max(float v) {
+  #pragma unroll
+  for (int off = WAVE / 2; off > 0; off >>= 1)
+    v = fmaxf(v, __shfl_down(v, off, WAVE));
+  return __shfl(v, 0, WAVE);
+}
+
 // Block-wide sum into a single float, returned valid in thread 0.
 // Requires blockDim.x <= 1024 (<= 16 waves); `scratch` needs >= 16 floats.
 __device__ __forceinline__ float block_reduce_sum(float v, float* scratch) {

@@ -298,18 +298,10 @@ class ApexTrainer:
                 # C51 projection loss (Bellemare et al. 2017); IS weights
                 # from the sampled priorities, priorities ← per-sample KL
                 from ..models.noisy import c51_loss
-                weights = None
-                if per_kw:
-                    N = per_kw["replay_size"]
-                    beta = per_kw["beta"]
-                    w = (per_kw["prios"] / per_kw["p_total"] * N) ** -beta
-                    w_max = (per_kw["p_min"] / per_kw["p_total"] * N) ** -beta
-                    weights = w / w_max
                 loss, td_abs = c51_loss(
                     self.model, self.target_model, batch["obs"],
                     batch["action"], batch["reward"], batch["discount"],
-                    batch["next_obs"], double=args.double_dqn,
-                    weights=weights)
+                    batch["next_obs"], double=args.double_dqn, **per_kw)
             else:
                 q = self.model(batch["obs"])
                 with torch.no_grad():

@@ -109,15 +109,12 @@ class DQNAgent(BaseAgent):
             p_total, p_min = self._per_stats
         if self.categorical:
             from ..models.noisy import c51_loss
-            from ..ops import per_is_weights
-            weights = None
-            if prios is not None:
-                weights = per_is_weights(prios, p_total, p_min, replay_size,
-                                         self.per_beta)
             self.model.train()
-            loss, td_abs = c51_loss(self.model, self.target_model, obs,
-                                    actions, rewards, discounts, next_obs,
-                                    double=args.double_dqn, weights=weights)
+            loss, td_abs = c51_loss(
+                self.model, self.target_model, obs, actions, rewards,
+                discounts, next_obs, double=args.double_dqn, prios=prios,
+                p_total=p_total, p_min=p_min, beta=self.per_beta,
+                replay_size=replay_size)
         else:
             loss, td_abs = fused_td_loss(
                 q, q_next_online, q_next_target, actions, rewards, discounts,

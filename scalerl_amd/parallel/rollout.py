@@ -108,6 +108,11 @@ class PinRegistry:
                                ctypes.c_uint(0)) == 0:
             self._ranges.append((ptr, nbytes))
             return nbytes
+        # not every platform can register memory the process already owns
+        # (virtualized GPUs refuse).  The refusal stays behind as the
+        # thread's last HIP error, which the next kernel-launch check would
+        # report as its own: read it back to clear it.
+        lib.hipGetLastError()
         return 0
 
     def pin_store(self, store: "RolloutStore") -> int:

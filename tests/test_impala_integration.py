@@ -87,6 +87,24 @@ def test_impala_learns_synthetic_reward(tmp_path):
 
 
 @pytest.mark.gpu
+def test_refused_host_registration_leaves_no_hip_error():
+    """Where hipHostRegister is refused, pin() reports 0 bytes and the
+    refusal must not surface at the next kernel launch."""
+    from scalerl_amd.parallel.rollout import PinRegistry
+    torch.cuda.init()
+    t = torch.zeros(1024).share_memory_()
+    pins = PinRegistry()
+    try:
+        assert pins.pin(t) in (0, t.numel() * t.element_size())
+        d = torch.ones(8, device="cuda:0")  # a launch, checked by torch
+        d.copy_(t[:8], non_blocking=True)
+        torch.cuda.synchronize()
+        assert d.sum().item() == 0.0
+    finally:
+        pins.unpin_all()
+
+
+@pytest.mark.gpu
 def test_impala_gpu_learner_end_to_end(tmp_path):
     """GPU learner + CPU actor inference: fused kernels in the loop."""
     t = ImpalaTrainer(_args(tmp_path, device="cuda:0", dtype="bf16"))

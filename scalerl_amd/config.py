@@ -180,9 +180,9 @@ class ImpalaArguments(RLArguments):
     checkpoint_path: str = _h("explicit checkpoint file (empty → auto)", default="")
     inference: str = _h("actor inference placement: cpu | gpu", default="cpu")
     inference_worker: str = _h(
-        "gpu-inference execution: 'process' = dedicated process (default; "
-        "a same-process 'thread' variant exists but aborts with HSA "
-        "exceptions on ROCm 7.2 — see profiles/README.md)",
+        "gpu-inference execution: 'process' = dedicated process (the "
+        "validated default); 'thread' = experimental same-process variant, "
+        "aborts with HSA exceptions on ROCm 7.2 — see docs/DEBUGGING.md",
         default="process")
     remote_actor_slots: int = _h("store slots reserved for remote-node "
                                  "actors (0 disables the TCP server)", default=0)

@@ -116,11 +116,15 @@ def inference_worker(device_index: int, model_kwargs: Dict, slots: InferenceSlot
     """Inference worker main — either a dedicated process (own HIP context)
     or a THREAD of the learner process on its own stream (``as_thread``).
 
-    The thread mode exists because hipGraph execution in one process with
-    concurrent HIP submissions from another is fragile on ROCm 7.2 (r1/r2
-    measured HSA_STATUS_ERROR_EXCEPTION aborts both during capture and
-    during replay); a same-context second stream plus
-    ``capture_error_mode="thread_local"`` is the supported shape for this.
+    The dedicated process is the validated default
+    (``ImpalaArguments.inference_worker = "process"``; what bench.py and
+    the GPU tests run).  The thread mode was written because hipGraph
+    execution in one process with concurrent HIP submissions from another
+    is fragile on ROCm 7.2 (HSA_STATUS_ERROR_EXCEPTION aborts during capture
+    and during replay; profiles/README.md finding 2), with a same-context
+    second stream plus ``capture_error_mode="thread_local"`` as the shape
+    meant to avoid that — but it aborts with HSA exceptions of its own,
+    with or without graphs (docs/DEBUGGING.md), and stays experimental.
     """
     from ..models.atari import AtariNet
     from .flat import FlatParams

@@ -24,6 +24,7 @@ so a 10 GbE link sustains ≈50k env-steps/s per node).
 from __future__ import annotations
 
 import threading
+from functools import partial
 from typing import Dict, List, Optional
 
 import torch
@@ -31,7 +32,7 @@ import torch.multiprocessing as mp
 
 from .cluster import RemoteWorkerCluster, WorkerServer
 from .flat import FlatParams
-from .rollout import RolloutStore, actor_loop
+from .rollout import RolloutStore, actor_loop, local_policy
 
 _SLOT_FIELDS = ("obs", "reward", "done", "last_action", "action", "logits",
                 "episode_return")
@@ -117,7 +118,8 @@ def remote_actor_node(host: str, port: int, num_actors: int = 4,
         p = ctx.Process(target=actor_loop,
                         args=(i, env_spec, store, free_q, full_q, stop,
                               counter),
-                        kwargs=dict(actor_model=model,
+                        kwargs=dict(policy_factory=partial(local_policy,
+                                                           model),
                                     seed=cfg.get("seed", 0)),
                         daemon=True)
         p.start()

@@ -133,14 +133,6 @@ def pin_tensor(t: torch.Tensor, registry: "PinRegistry" = None) -> int:
     return reg.pin(t)
 
 
-def pin_store(store: RolloutStore, registry: "PinRegistry" = None) -> int:
-    """hipHostRegister every shared slot tensor in THIS process so H2D
-    copies from them are async DMA.  Registration is per-process; call it
-    from the learner after CUDA init.  Returns bytes pinned (0 = no-op)."""
-    reg = registry or PinRegistry()
-    return reg.pin_store(store)
-
-
 class LocalPolicy:
     """CPU inference against the shared-flat-aliased model (the reference's
     per-actor inference mode, impala_atari.py:196-198).  Same call contract
@@ -181,6 +173,43 @@ class ActorState:
         self.episode_return = torch.zeros(E)
 
 
+def _write_row(state: ActorState, store: RolloutStore, slot: int, row: int,
+               episode_return: torch.Tensor) -> None:
+    store.obs[slot, row].copy_(state.obs)
+    store.reward[slot, row].copy_(state.reward)
+    store.done[slot, row].copy_(state.done)
+    store.last_action[slot, row].copy_(state.last_action)
+    store.episode_return[slot, row].copy_(episode_return)
+
+
+def write_row0(state: ActorState, store: RolloutStore, slot: int) -> None:
+    """Row 0 = carried-over env output (the continuation row)."""
+    _write_row(state, store, slot, 0, state.episode_return)
+
+
+def rollout_step(state: ActorState, store: RolloutStore, slot: int, t: int,
+                 action, logits, snap) -> None:
+    """The step body every rollout shares: record the decision taken at row
+    ``t``, step the env, account episode returns, write row ``t + 1``."""
+    if snap is not None:
+        store.core_state[slot].copy_(snap)
+    store.action[slot, t].copy_(action)
+    store.logits[slot, t].copy_(logits)
+
+    obs_np, rew_np, done_np = state.env.step(action.numpy())
+    # episode accounting: returns BEFORE reset (reward of this step incl.)
+    state.episode_return += torch.from_numpy(rew_np)
+    ep_ret = state.episode_return.clone()
+    done_t = torch.from_numpy(done_np)
+    state.episode_return[done_t] = 0.0
+
+    state.obs = torch.from_numpy(np.ascontiguousarray(obs_np))
+    state.reward = torch.from_numpy(rew_np)
+    state.done = done_t
+    state.last_action = action
+    _write_row(state, store, slot, t + 1, ep_ret)
+
+
 @torch.no_grad()
 def run_rollout(state: ActorState, store: RolloutStore, slot: int) -> int:
     """Fill one slot (T env steps across E envs).  Returns env steps done.
@@ -190,51 +219,13 @@ def run_rollout(state: ActorState, store: RolloutStore, slot: int) -> int:
     decisions (row T's decision belongs to the next slot's row 0).
     """
     T = store.rollout_length
-    E = store.envs_per_slot
-
-    # row 0 = carried-over env output (the continuation row)
-    store.obs[slot, 0].copy_(state.obs)
-    store.reward[slot, 0].copy_(state.reward)
-    store.done[slot, 0].copy_(state.done)
-    store.last_action[slot, 0].copy_(state.last_action)
-    store.episode_return[slot, 0].copy_(state.episode_return)
-
+    write_row0(state, store, slot)
     for t in range(T):
         action, logits, snap = state.policy(
             state.obs, state.reward, state.done, state.last_action,
             want_state=(t == 0 and store.core_state is not None))
-        if snap is not None:
-            store.core_state[slot].copy_(snap)
-        store.action[slot, t].copy_(action)
-        store.logits[slot, t].copy_(logits)
-
-        obs_np, rew_np, done_np = state.env.step(action.numpy())
-        # episode accounting: returns BEFORE reset (reward of this step incl.)
-        state.episode_return += torch.from_numpy(rew_np)
-        ep_ret = state.episode_return.clone()
-        done_t = torch.from_numpy(done_np)
-        state.episode_return[done_t] = 0.0
-
-        state.obs = torch.from_numpy(np.ascontiguousarray(obs_np))
-        state.reward = torch.from_numpy(rew_np)
-        state.done = done_t
-        state.last_action = action
-
-        row = t + 1
-        store.obs[slot, row].copy_(state.obs)
-        store.reward[slot, row].copy_(state.reward)
-        store.done[slot, row].copy_(state.done)
-        store.last_action[slot, row].copy_(action)
-        store.episode_return[slot, row].copy_(ep_ret)
-    return T * E
-
-
-def write_row0(state: ActorState, store: RolloutStore, slot: int) -> None:
-    store.obs[slot, 0].copy_(state.obs)
-    store.reward[slot, 0].copy_(state.reward)
-    store.done[slot, 0].copy_(state.done)
-    store.last_action[slot, 0].copy_(state.last_action)
-    store.episode_return[slot, 0].copy_(state.episode_return)
+        rollout_step(state, store, slot, t, action, logits, snap)
+    return T * store.envs_per_slot
 
 
 @torch.no_grad()
@@ -245,7 +236,6 @@ def run_rollout_db(states, store: RolloutStore, slots) -> int:
     single-group path pays the full round latency every step).
     Policies must expose request()/wait() (RemotePolicy)."""
     T = store.rollout_length
-    E = store.envs_per_slot
     want0 = store.core_state is not None
     for g in (0, 1):
         write_row0(states[g], store, slots[g])
@@ -255,33 +245,12 @@ def run_rollout_db(states, store: RolloutStore, slots) -> int:
     for t in range(T):
         for g in (0, 1):
             st = states[g]
-            slot = slots[g]
             action, logits, snap = st.policy.wait()
-            if snap is not None:
-                store.core_state[slot].copy_(snap)
-            store.action[slot, t].copy_(action)
-            store.logits[slot, t].copy_(logits)
-
-            obs_np, rew_np, done_np = st.env.step(action.numpy())
-            st.episode_return += torch.from_numpy(rew_np)
-            ep_ret = st.episode_return.clone()
-            done_t = torch.from_numpy(done_np)
-            st.episode_return[done_t] = 0.0
-            st.obs = torch.from_numpy(np.ascontiguousarray(obs_np))
-            st.reward = torch.from_numpy(rew_np)
-            st.done = done_t
-            st.last_action = action
-
-            row = t + 1
-            store.obs[slot, row].copy_(st.obs)
-            store.reward[slot, row].copy_(st.reward)
-            store.done[slot, row].copy_(st.done)
-            store.last_action[slot, row].copy_(action)
-            store.episode_return[slot, row].copy_(ep_ret)
+            rollout_step(st, store, slots[g], t, action, logits, snap)
             if t + 1 < T:
                 st.policy.request(st.obs, st.reward, st.done,
                                   st.last_action)
-    return 2 * T * E
+    return 2 * T * store.envs_per_slot
 
 
 def build_actor_env(env_spec: dict, actor_id: int):
@@ -308,29 +277,59 @@ def build_actor_env(env_spec: dict, actor_id: int):
         for i in range(E)])
 
 
+def local_policy(model, actor_id: int, num_envs: int) -> LocalPolicy:
+    """Policy factory (see :func:`actor_loop`): CPU inference on ``model``,
+    whose params alias the published shared flat buffer."""
+    model.eval()
+    return LocalPolicy(model, num_envs)
+
+
+def remote_policy(inf_slots, inf_req_q, inf_sem, actor_id: int,
+                  num_envs: int):
+    """Policy factory (see :func:`actor_loop`): the actor's row of the GPU
+    inference worker's request/response slots."""
+    from .inference import RemotePolicy
+    return RemotePolicy(actor_id, inf_slots, inf_req_q, inf_sem)
+
+
+def _actor_init(actor_id: int, seed: int, torch_threads: int) -> None:
+    torch.manual_seed(seed + actor_id)
+    torch.set_num_threads(torch_threads)
+
+
+def _report_episodes(episode_queue, store: RolloutStore, slots) -> None:
+    """Completed-episode returns of the given slots, for logging (best
+    effort: dropped when the queue is full)."""
+    if episode_queue is None:
+        return
+    rets = []
+    for slot in slots:
+        mask = store.done[slot, 1:].numpy()
+        if mask.any():
+            rets.extend(store.episode_return[slot, 1:].numpy()[mask].tolist())
+    if rets:
+        try:
+            episode_queue.put_nowait(rets)
+        except queue.Full:
+            pass
+
+
 def actor_loop(actor_id: int, env_spec: dict, store: RolloutStore,
-               free_q, full_q, stop_event, step_counter,
-               episode_queue=None, seed: int = 0, actor_model=None,
-               inf_slots=None, inf_req_q=None, inf_sem=None,
-               torch_threads: int = 1):
-    """Actor process main (reference: impala_atari.py:153-220).
+               free_q, full_q, stop_event, step_counter, policy_factory,
+               episode_queue=None, seed: int = 0, torch_threads: int = 1):
+    """Actor process main for every actor-learner trainer (reference:
+    impala_atari.py:153-220).
 
     Runs under the *spawn* start method (the learner initializes HIP, so
     forked children would inherit a poisoned runtime): every argument is
-    picklable; shared tensors travel as shm handles.  Policy: RemotePolicy
-    when inference-slot plumbing is given, else LocalPolicy on
-    ``actor_model`` (whose params alias the published shared flat buffer).
+    picklable; shared tensors travel as shm handles.  ``policy_factory`` is
+    therefore a module-level callable or a ``functools.partial`` of one,
+    called as ``policy_factory(actor_id, num_envs)`` once the env exists.
     Poison pill: a None on free_q exits.
     """
-    torch.manual_seed(seed + actor_id)
-    torch.set_num_threads(torch_threads)
+    _actor_init(actor_id, seed, torch_threads)
     env = build_actor_env(env_spec, actor_id)
-    if inf_slots is not None:
-        from .inference import RemotePolicy
-        policy = RemotePolicy(actor_id, inf_slots, inf_req_q, inf_sem)
-    else:
-        actor_model.eval()
-        policy = LocalPolicy(actor_model, store.envs_per_slot)
+    policy = policy_factory(actor_id, store.envs_per_slot)
     state = ActorState(env, policy, store.envs_per_slot)
     try:
         while not stop_event.is_set():
@@ -341,15 +340,7 @@ def actor_loop(actor_id: int, env_spec: dict, store: RolloutStore,
             full_q.put(slot)
             with step_counter.get_lock():
                 step_counter.value += steps
-            if episode_queue is not None:
-                # completed-episode returns for logging (best effort)
-                mask = store.done[slot, 1:].numpy()
-                if mask.any():
-                    rets = store.episode_return[slot, 1:].numpy()[mask]
-                    try:
-                        episode_queue.put_nowait(rets.tolist())
-                    except queue.Full:
-                        pass
+            _report_episodes(episode_queue, store, (slot,))
     except KeyboardInterrupt:
         pass
 
@@ -362,16 +353,14 @@ def actor_loop_db(actor_id: int, env_spec: dict, store: RolloutStore,
     """Double-buffered actor process main: two env groups (rows
     ``row_ids`` in the inference slots), each filling its own rollout slot,
     interleaved via :func:`run_rollout_db`.  Poison pill: None on free_q."""
-    import queue as _q
-    from .inference import RemotePolicy
-    torch.manual_seed(seed + actor_id)
-    torch.set_num_threads(torch_threads)
+    _actor_init(actor_id, seed, torch_threads)
     states = []
     for g in (0, 1):
         spec = dict(env_spec)
         spec["seed"] = env_spec.get("seed", 0) + 500_000 * g
         env = build_actor_env(spec, actor_id)
-        policy = RemotePolicy(row_ids[g], inf_slots, inf_req_q, inf_sems[g])
+        policy = remote_policy(inf_slots, inf_req_q, inf_sems[g], row_ids[g],
+                               store.envs_per_slot)
         states.append(ActorState(env, policy, store.envs_per_slot))
     try:
         while not stop_event.is_set():
@@ -386,19 +375,7 @@ def actor_loop_db(actor_id: int, env_spec: dict, store: RolloutStore,
             full_q.put(slot_b)
             with step_counter.get_lock():
                 step_counter.value += steps
-            if episode_queue is not None:
-                rets = []
-                for slot in (slot_a, slot_b):
-                    mask = store.done[slot, 1:].numpy()
-                    if mask.any():
-                        rets.extend(
-                            store.episode_return[slot, 1:].numpy()[mask]
-                            .tolist())
-                if rets:
-                    try:
-                        episode_queue.put_nowait(rets)
-                    except _q.Full:
-                        pass
+            _report_episodes(episode_queue, store, (slot_a, slot_b))
     except KeyboardInterrupt:
         pass
 
@@ -485,9 +462,6 @@ class BatchGatherer:
     def gather(self, slot_ids: List[int]) -> Dict[str, torch.Tensor]:
         """Synchronous convenience path (tests, non-pipelined callers)."""
         return self.finish(self.start(slot_ids))
-
-    def copies_done(self) -> None:
-        """Back-compat no-op: finish() already syncs the copy event."""
 
     def _to_batch_layout(self, name: str, stacked: torch.Tensor) -> torch.Tensor:
         """[K, T+1, E, ...] → [T+1, K*E, ...]; core_state → [L, K*E, H] x2."""

@@ -20,21 +20,20 @@ from __future__ import annotations
 
 import os
 import time
-from typing import Dict, List, Optional
+from functools import partial
+from typing import Dict, Optional
 
 import torch
 import torch.nn.functional as F
-import torch.multiprocessing as mp
 
 from ..config import A3CGpuArguments
 from ..models.a3c_atari import A3CAtariNet
 from ..ops import FusedAdam, clip_grad_norm_
 from ..ops.scans import gae as gae_op
-from ..parallel import FlatParams, all_reduce_flat, get_rank, get_world_size
-from ..parallel.rollout import (ActorState, RolloutStore, build_actor_env,
-                                BatchGatherer, run_rollout)
-from ..utils import Timings, get_logger
+from ..parallel import FlatParams, all_reduce_flat
+from ..parallel.rollout import BatchGatherer, RolloutStore, actor_loop
 from ..utils.checkpoint import save_checkpoint
+from .actor_learner import ActorLearnerTrainer
 
 
 class A3CLocalPolicy:
@@ -59,49 +58,17 @@ class A3CLocalPolicy:
         return action, logits, snap
 
 
-def a3c_actor_loop(actor_id: int, env_spec: dict, store: RolloutStore,
-                   free_q, full_q, stop_event, step_counter,
-                   actor_model=None, episode_queue=None, seed: int = 0):
-    """Actor process main (mirrors parallel/rollout.actor_loop with the
-    A3C policy; reference: parallel_a3c.py:327-389 rollout phase)."""
-    import queue as _queue
-    torch.manual_seed(seed + actor_id)
-    torch.set_num_threads(1)
-    env = build_actor_env(env_spec, actor_id)
-    actor_model.eval()
-    policy = A3CLocalPolicy(actor_model, store.envs_per_slot)
-    state = ActorState(env, policy, store.envs_per_slot)
-    try:
-        while not stop_event.is_set():
-            slot = free_q.get()
-            if slot is None:
-                break
-            steps = run_rollout(state, store, slot)
-            full_q.put(slot)
-            with step_counter.get_lock():
-                step_counter.value += steps
-            if episode_queue is not None:
-                mask = store.done[slot, 1:].numpy()
-                if mask.any():
-                    rets = store.episode_return[slot, 1:].numpy()[mask]
-                    try:
-                        episode_queue.put_nowait(rets.tolist())
-                    except _queue.Full:
-                        pass
-    except KeyboardInterrupt:
-        pass
+def a3c_local_policy(model: A3CAtariNet, actor_id: int,
+                     num_envs: int) -> A3CLocalPolicy:
+    """Policy factory for :func:`scalerl_amd.parallel.rollout.actor_loop`
+    (reference: parallel_a3c.py:327-389 rollout phase)."""
+    model.eval()
+    return A3CLocalPolicy(model, num_envs)
 
 
-class A3CGpuTrainer:
+class A3CGpuTrainer(ActorLearnerTrainer):
     def __init__(self, args: A3CGpuArguments, device: Optional[str] = None):
-        self.args = args
-        self.rank = get_rank()
-        self.world_size = get_world_size()
-        self.log = get_logger("a3c-gpu")
-        if device is None:
-            device = ("cuda" if torch.cuda.is_available() else "cpu") \
-                if args.device == "auto" else args.device
-        self.device = torch.device(device)
+        super().__init__(args, device, "a3c-gpu")
 
         # probe the 42×42 wrapped env for shapes
         from ..envs.a3c_env import create_atari_env
@@ -111,54 +78,29 @@ class A3CGpuTrainer:
         probe.close()
 
         E = args.envs_per_actor
-        K = args.slots_per_batch
-        num_slots = args.num_actors + 2 * K + 2
+        self.slots_per_batch = args.slots_per_batch
+        self.local_slots = args.num_actors + 2 * self.slots_per_batch + 2
+        # CPU phase (precedes any HIP initialization)
         torch.manual_seed(args.seed + self.rank)
         self.actor_model = A3CAtariNet(self.obs_shape[0], self.num_actions)
         self.actor_model.eval()
         self.shared_flat = FlatParams(self.actor_model, device="cpu",
                                       share=True)
         self.store = RolloutStore(
-            num_slots, args.rollout_steps, E, self.obs_shape,
+            self.local_slots, args.rollout_steps, E, self.obs_shape,
             self.num_actions, lstm_layers=1, lstm_hidden=256,
             obs_dtype=torch.float32)
 
-        self._mp_ctx = ("fork" if (self.device.type == "cpu"
-                                   and not torch.cuda.is_initialized()
-                                   and not os.environ.get(
-                                       "SCALERL_FORCE_SPAWN"))
-                        else "spawn")
-        ctx = mp.get_context(self._mp_ctx)
-        self.free_q = ctx.SimpleQueue()
-        self.full_q = ctx.Queue()
-        self.stop_event = ctx.Event()
-        self.step_counter = ctx.Value("l", 0)
-        self.episode_q = ctx.Queue(maxsize=256)
-        self.actors: List[mp.Process] = []
-        self.global_step = 0
-        self.learn_iters = 0
-        self.timings = Timings()
-        self._pending = None
-        self._num_slots = num_slots
-
     # -- lifecycle ---------------------------------------------------------
-    def start_actors(self) -> None:
+    def _actor_process(self, i: int):
         args = self.args
-        ctx = mp.get_context(self._mp_ctx)
         env_spec = {"env_id": args.env_id, "envs_per_actor": args.envs_per_actor,
                     "seed": args.seed + 7919 * self.rank, "a3c_wrap": True}
-        for i in range(args.num_actors):
-            p = ctx.Process(
-                target=a3c_actor_loop,
-                args=(i, env_spec, self.store, self.free_q, self.full_q,
-                      self.stop_event, self.step_counter),
-                kwargs=dict(actor_model=self.actor_model, seed=args.seed,
-                            episode_queue=self.episode_q),
-                daemon=True, name=f"a3c-actor-{self.rank}-{i}")
-            p.start()
-            self.actors.append(p)
-        for s in range(self._num_slots):
-            self.free_q.put(s)
+        return (actor_loop, self._actor_args(i, env_spec),
+                dict(policy_factory=partial(a3c_local_policy,
+                                            self.actor_model),
+                     seed=args.seed, episode_queue=self.episode_q),
+                f"a3c-actor-{self.rank}-{i}")
 
     def setup_learner(self) -> None:
         args = self.args
@@ -174,13 +116,7 @@ class A3CGpuTrainer:
                                       args.slots_per_batch)
         if self.device.type == "cuda":
             torch.backends.cudnn.benchmark = True
-            from ..parallel.rollout import PinRegistry
-            self._pins = PinRegistry()
-            pinned = self._pins.pin_store(self.store)
-            pinned += self._pins.pin(self.shared_flat.flat)
-            self.log.info(f"pinned {pinned / 1e6:.1f} MB")
-        else:
-            self._pins = None
+            self._pin_host_memory()
         self._publish()
         self.autocast_dtype = (torch.bfloat16 if args.dtype == "bf16" and
                                self.device.type == "cuda" else None)
@@ -190,32 +126,6 @@ class A3CGpuTrainer:
         self.shared_flat.flat.copy_(self.flat.flat)
 
     # -- core step ---------------------------------------------------------
-    def _dequeue_batch(self):
-        import queue as _queue
-        slot_ids = []
-        while len(slot_ids) < self.args.slots_per_batch:
-            try:
-                slot_ids.append(self.full_q.get(timeout=30.0))
-            except _queue.Empty:
-                dead = [p.name for p in self.actors if not p.is_alive()]
-                if dead:
-                    raise RuntimeError(f"actor process(es) died: {dead}")
-        self.timings.time("dequeue")
-        return slot_ids
-
-    def next_batch(self) -> Dict[str, torch.Tensor]:
-        if self._pending is None:
-            ids = self._dequeue_batch()
-            self._pending = (self.gatherer.start(ids), ids)
-        token, ids = self._pending
-        batch = self.gatherer.finish(token)
-        self.timings.time("gather_wait")
-        for s in ids:
-            self.free_q.put(s)
-        nxt = self._dequeue_batch()
-        self._pending = (self.gatherer.start(nxt), nxt)
-        return batch
-
     def learn_step(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         args = self.args
         self.model.train()
@@ -288,18 +198,3 @@ class A3CGpuTrainer:
                                 hparam=vars(args),
                                 extra={"global_step": self.global_step})
             self.shutdown()
-
-    def shutdown(self) -> None:
-        self.stop_event.set()
-        for _ in self.actors:
-            self.free_q.put(None)
-        for p in self.actors:
-            p.join(timeout=2.0)
-            if p.is_alive():
-                p.terminate()
-        self.actors.clear()
-        if getattr(self, "_pins", None) is not None:
-            if self.device.type == "cuda":
-                torch.cuda.synchronize()
-            self._pins.unpin_all()
-            self._pins = None

@@ -25,22 +25,22 @@ apex/memory.py semantics; Horgan et al. 2018):
 
 from __future__ import annotations
 
-from typing import Dict, List, Optional
+from functools import partial
+from typing import Dict, Optional
 
 import numpy as np
 import torch
-import torch.multiprocessing as mp
 
 from ..config import ApexArguments
 from ..data import PrioritizedReplayBuffer
 from ..models.atari import AtariQNet
 from ..ops import (FusedAdam, clip_grad_norm_, fused_polyak_, fused_td_loss,
                    nstep_fold)
-from ..parallel import FlatParams, all_reduce_flat, get_rank, get_world_size
-from ..parallel.rollout import RolloutStore, build_actor_env
-from ..utils import get_logger
+from ..parallel import FlatParams, all_reduce_flat, get_world_size
+from ..parallel.rollout import RolloutStore, actor_loop
 from ..utils.checkpoint import save_agent_checkpoint
 from ..envs.synthetic import SyntheticAtariVecEnv
+from .actor_learner import ActorLearnerTrainer
 
 
 class EpsGreedyPolicy:
@@ -69,38 +69,16 @@ class EpsGreedyPolicy:
         return action, q, None
 
 
-def apex_actor_loop(actor_id: int, env_spec: dict, store: RolloutStore,
-                    free_q, full_q, stop_event, step_counter, actor_model,
-                    eps: float, seed: int = 0):
-    from ..parallel.rollout import ActorState, run_rollout
-    torch.manual_seed(seed + actor_id)
-    torch.set_num_threads(1)
-    actor_model.eval()
-    env = build_actor_env(env_spec, actor_id)
-    policy = EpsGreedyPolicy(actor_model, eps, seed=seed + actor_id)
-    state = ActorState(env, policy, store.envs_per_slot)
-    try:
-        while not stop_event.is_set():
-            slot = free_q.get()
-            if slot is None:
-                break
-            steps = run_rollout(state, store, slot)
-            full_q.put(slot)
-            with step_counter.get_lock():
-                step_counter.value += steps
-    except KeyboardInterrupt:
-        pass
+def eps_greedy_policy(model: AtariQNet, eps: float, seed: int,
+                      actor_id: int, num_envs: int) -> EpsGreedyPolicy:
+    """Policy factory for :func:`scalerl_amd.parallel.rollout.actor_loop`."""
+    model.eval()
+    return EpsGreedyPolicy(model, eps, seed=seed)
 
 
-class ApexTrainer:
+class ApexTrainer(ActorLearnerTrainer):
     def __init__(self, args: ApexArguments, device: Optional[str] = None):
-        self.args = args
-        self.rank = get_rank()
-        self.log = get_logger("apex")
-        if device is None:
-            device = ("cuda" if torch.cuda.is_available() else "cpu") \
-                if args.device == "auto" else args.device
-        self.device = torch.device(device)
+        super().__init__(args, device, "apex", episode_q=False)
 
         probe = SyntheticAtariVecEnv(1)
         self.obs_shape = probe.observation_space.shape
@@ -109,28 +87,16 @@ class ApexTrainer:
         E = args.envs_per_actor
         self.chunk_len = 32  # transitions per slot row-block
         self.categorical = getattr(args, "categorical_dqn", False)
+        # CPU phase (precedes any HIP initialization)
         torch.manual_seed(args.seed + self.rank)
         self.actor_model = self._build_qnet()
         self.actor_model.eval()
         self.shared_flat = FlatParams(self.actor_model, device="cpu",
                                       share=True)
+        self.local_slots = 2 * args.num_actors + 4
         self.store = RolloutStore(
-            2 * args.num_actors + 4, self.chunk_len, E, self.obs_shape,
+            self.local_slots, self.chunk_len, E, self.obs_shape,
             self.num_actions, lstm_hidden=0)
-        import os as _os
-        self._mp_ctx = ("fork" if (self.device.type == "cpu"
-                                   and not torch.cuda.is_initialized()
-                                   and not _os.environ.get(
-                                       "SCALERL_FORCE_SPAWN"))
-                        else "spawn")
-        ctx = mp.get_context(self._mp_ctx)
-        self.free_q = ctx.SimpleQueue()
-        self.full_q = ctx.Queue()  # timeout-capable: the learner watchdogs it
-        self.stop_event = ctx.Event()
-        self.step_counter = ctx.Value("l", 0)
-        self.actors: List[mp.Process] = []
-        self.global_step = 0
-        self.learn_iters = 0
 
     def _build_qnet(self):
         args = self.args
@@ -146,23 +112,16 @@ class ApexTrainer:
         n = max(self.args.num_actors - 1, 1)
         return self.args.eps_base ** (1 + i / n * self.args.eps_alpha)
 
-    def start_actors(self) -> None:
+    def _actor_process(self, i: int):
         args = self.args
-        ctx = mp.get_context(self._mp_ctx)
         env_spec = {"env_id": args.env_id,
                     "envs_per_actor": args.envs_per_actor,
                     "seed": args.seed + 104729 * self.rank}
-        for i in range(args.num_actors):
-            p = ctx.Process(
-                target=apex_actor_loop,
-                args=(i, env_spec, self.store, self.free_q, self.full_q,
-                      self.stop_event, self.step_counter, self.actor_model,
-                      self.actor_eps(i), args.seed),
-                daemon=True, name=f"apex-actor-{self.rank}-{i}")
-            p.start()
-            self.actors.append(p)
-        for s in range(self.store.num_slots):
-            self.free_q.put(s)
+        factory = partial(eps_greedy_policy, self.actor_model,
+                          self.actor_eps(i), args.seed + i)
+        return (actor_loop, self._actor_args(i, env_spec),
+                dict(policy_factory=factory, seed=args.seed),
+                f"apex-actor-{self.rank}-{i}")
 
     def setup_learner(self) -> None:
         args = self.args
@@ -192,10 +151,7 @@ class ApexTrainer:
                 device=dev, gamma=args.gamma, seed=args.seed)
         self.beta_per = args.per_beta
         if dev.type == "cuda":
-            from ..parallel.rollout import PinRegistry
-            self._pins = PinRegistry()
-            self._pins.pin_store(self.store)
-            self._pins.pin(self.shared_flat.flat)
+            self._pin_host_memory()
             self._ingest_done = torch.cuda.Event()
         self._publish()
 
@@ -255,18 +211,11 @@ class ApexTrainer:
         # outproduce the ingest forward would live-lock the learner here
         ingested = 0
         max_slots = 4
-        import queue as _queue
         for _ in range(max_slots):
             if self.full_q.empty():
                 if len(self.buffer) >= args.warmup_learn_steps or ingested:
                     break
-            try:
-                slot = self.full_q.get(timeout=60.0)
-            except _queue.Empty:
-                dead = [p.name for p in self.actors if not p.is_alive()]
-                if dead:
-                    raise RuntimeError(f"actor process(es) died: {dead}")
-                continue
+            slot = self._get_full_slot()
             ingested += self.ingest_slot(slot)
             # the H2D copies out of the hipHostRegister'd shared slot are
             # async: fence them before recycling the slot, or an actor can
@@ -338,21 +287,6 @@ class ApexTrainer:
                               actor_target=self.target_model,
                               extra={"optimizer_state_dict":
                                      self.optimizer.state_dict()})
-
-    def shutdown(self) -> None:
-        self.stop_event.set()
-        for _ in self.actors:
-            self.free_q.put(None)
-        for p in self.actors:
-            p.join(timeout=2.0)
-            if p.is_alive():
-                p.terminate()
-        self.actors.clear()
-        if getattr(self, "_pins", None) is not None:
-            if self.device.type == "cuda":
-                torch.cuda.synchronize()
-            self._pins.unpin_all()
-            self._pins = None
 
 
 class ParallelDQNTrainer(ApexTrainer):

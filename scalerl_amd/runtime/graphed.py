@@ -22,16 +22,52 @@ from typing import Dict, Tuple
 import torch
 
 
-class GraphedImpalaStep:
-    def __init__(self, model, flat_grad: torch.Tensor, loss_kwargs: Dict,
-                 batch_example: Dict[str, torch.Tensor], use_lstm: bool,
-                 autocast_dtype, reward_clip: bool, discounting: float,
-                 warmup_iters: int = 3):
-        from ..ops import impala_loss
+def impala_fwd_bwd(model, flat_grad: torch.Tensor,
+                   batch: Dict[str, torch.Tensor], *, use_lstm: bool,
+                   autocast_dtype, reward_clip: bool, discounting: float,
+                   loss_kwargs: Dict, timings=None):
+    """{zero-grad → model fwd → fused V-trace/loss → backward} of the IMPALA
+    learner: the one definition, run eagerly by ``ImpalaTrainer`` and
+    captured by :class:`GraphedImpalaStep`.  ``timings`` marks ``forward`` /
+    ``backward`` on the eager path; it is None under capture (no host
+    timing belongs inside a captured region).  Returns (total, comps)."""
+    from ..ops import impala_loss
 
-        self.model = model
-        self.flat_grad = flat_grad
-        self.use_lstm = use_lstm
+    flat_grad.zero_()
+    inputs = {k: batch[k] for k in ("obs", "reward", "done", "last_action")}
+    core_state = ()
+    if use_lstm:
+        cs = batch["core_state"]
+        core_state = (cs[0], cs[1])
+    if autocast_dtype is not None:
+        with torch.autocast(device_type="cuda", dtype=autocast_dtype):
+            out, _ = model(inputs, core_state, greedy=True)
+    else:
+        out, _ = model(inputs, core_state, greedy=True)
+    logits = out["policy_logits"].float()
+    baseline = out["baseline"].float()
+    rewards = batch["reward"][1:]
+    if reward_clip:
+        rewards = torch.clamp(rewards, -1, 1)
+    discounts = (~batch["done"][1:]).float() * discounting
+    total, comps, _ = impala_loss(
+        batch["logits"][:-1], logits[:-1], batch["action"][:-1],
+        rewards, discounts, baseline[:-1], baseline[-1].detach(),
+        **loss_kwargs)
+    if timings is not None:
+        timings.time("forward")
+    total.backward()
+    if timings is not None:
+        timings.time("backward")
+    return total.detach(), comps
+
+
+class GraphedImpalaStep:
+    def __init__(self, model, flat_grad: torch.Tensor,
+                 batch_example: Dict[str, torch.Tensor],
+                 warmup_iters: int = 3, **step_kwargs):
+        """``step_kwargs``: the keyword arguments of :func:`impala_fwd_bwd`
+        (``timings`` excepted)."""
         dev = flat_grad.device
 
         # static input buffers (graph reads these addresses every replay),
@@ -42,30 +78,8 @@ class GraphedImpalaStep:
         }
 
         def run_step():
-            self.flat_grad.zero_()
-            inputs = {k: self.static[k]
-                      for k in ("obs", "reward", "done", "last_action")}
-            core_state = ()
-            if use_lstm:
-                cs = self.static["core_state"]
-                core_state = (cs[0], cs[1])
-            if autocast_dtype is not None:
-                with torch.autocast(device_type="cuda", dtype=autocast_dtype):
-                    out, _ = model(inputs, core_state, greedy=True)
-            else:
-                out, _ = model(inputs, core_state, greedy=True)
-            logits = out["policy_logits"].float()
-            baseline = out["baseline"].float()
-            rewards = self.static["reward"][1:]
-            if reward_clip:
-                rewards = torch.clamp(rewards, -1, 1)
-            discounts = (~self.static["done"][1:]).float() * discounting
-            total, comps, _ = impala_loss(
-                self.static["logits"][:-1], logits[:-1],
-                self.static["action"][:-1], rewards, discounts,
-                baseline[:-1], baseline[-1].detach(), **loss_kwargs)
-            total.backward()
-            return total.detach(), comps
+            return impala_fwd_bwd(model, flat_grad, self.static,
+                                  **step_kwargs)
 
         # The C++ LSTM sequence loop (ops/csrc/lstm_seq.hip) drives raw
         # rocBLAS calls that are not graph-capture-safe (r2 call-2 finding:

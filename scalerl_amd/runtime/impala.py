@@ -25,6 +25,7 @@ from __future__ import annotations
 
 import os
 import time
+from functools import partial
 from typing import Dict, List, Optional
 
 import torch
@@ -33,24 +34,19 @@ import torch.multiprocessing as mp
 from ..config import ImpalaArguments
 from ..envs.synthetic import SyntheticAtariVecEnv
 from ..models.atari import AtariNet
-from ..ops import FusedRMSprop, clip_grad_norm_, impala_loss
-from ..parallel import FlatParams, all_reduce_flat, get_rank, get_world_size
+from ..ops import FusedRMSprop, clip_grad_norm_
+from ..parallel import FlatParams, all_reduce_flat
 from ..parallel.inference import InferenceSlots, inference_worker
-from ..parallel.rollout import BatchGatherer, RolloutStore, actor_loop
-from ..utils import Timings, get_logger
+from ..parallel.rollout import (BatchGatherer, RolloutStore, actor_loop,
+                                actor_loop_db, local_policy, remote_policy)
 from ..utils.checkpoint import load_checkpoint, save_checkpoint
+from . import graphed
+from .actor_learner import ActorLearnerTrainer
 
 
-class ImpalaTrainer:
+class ImpalaTrainer(ActorLearnerTrainer):
     def __init__(self, args: ImpalaArguments, device: Optional[str] = None):
-        self.args = args
-        self.rank = get_rank()
-        self.world_size = get_world_size()
-        self.log = get_logger("impala")
-        if device is None:
-            device = ("cuda" if torch.cuda.is_available() else "cpu") \
-                if args.device == "auto" else args.device
-        self.device = torch.device(device)
+        super().__init__(args, device, "impala")
 
         # ---- shapes ----
         probe_env = SyntheticAtariVecEnv(1) if args.env_id == "synthetic-atari" \
@@ -70,19 +66,21 @@ class ImpalaTrainer:
             f"batch_size ({args.batch_size}) must be a multiple of " \
             f"envs_per_actor ({E})"
         self.slots_per_batch = args.batch_size // E
+
+        # ---- inference placement ----
+        self.inference = args.inference
+        if self.inference == "gpu" and self.device.type != "cuda":
+            self.inference = "cpu"
         # double-buffered actors run two env groups, so each holds TWO
         # slots in flight (gpu-inference only; see actor_loop_db)
-        effective_inference = args.inference
-        if effective_inference == "gpu" and self.device.type != "cuda":
-            effective_inference = "cpu"
         self.double_buffer = bool(args.actor_double_buffer) and \
-            effective_inference == "gpu"
-        per_actor_slots = 2 if self.double_buffer else 1
+            self.inference == "gpu"
+        self._pills_per_actor = 2 if self.double_buffer else 1
         # enough slots that every actor can have its group(s) in flight
         # plus two batches queued; more would grow host shm for no
         # throughput (8 ranks x 24 actors x 290 MB slots must fit /dev/shm)
         num_buffers = args.num_buffers or (
-            per_actor_slots * args.num_actors +
+            self._pills_per_actor * args.num_actors +
             2 * self.slots_per_batch + 2)
         self.local_slots = num_buffers
         num_buffers += args.remote_actor_slots  # reserved tail ids
@@ -99,33 +97,11 @@ class ImpalaTrainer:
         self.store = RolloutStore(
             num_buffers, args.rollout_length, E, self.obs_shape,
             self.num_actions, lstm_layers=2, lstm_hidden=lstm_hidden)
-
-        # spawn, not fork, whenever the GPU is involved: the learner (and
-        # inference worker) initialize the HIP runtime, which does not
-        # survive fork on ROCm.  Shared-memory tensors travel to spawned
-        # children as shm handles.  Pure-CPU runs keep fork (fast startup).
-        self._mp_ctx = ("fork" if (self.device.type == "cpu"
-                                   and not torch.cuda.is_initialized()
-                                   and not os.environ.get(
-                                       "SCALERL_FORCE_SPAWN"))
-                        else "spawn")
-        ctx = mp.get_context(self._mp_ctx)
-        self.free_q = ctx.SimpleQueue()
-        self.full_q = ctx.Queue()  # timeout-capable: the learner watchdogs it
-        self.stop_event = ctx.Event()
-        self.step_counter = ctx.Value("l", 0)
-        self.episode_q = ctx.Queue(maxsize=256)
-        self.actors: List[mp.Process] = []
-        self._started = False
         self._num_buffers = num_buffers
 
-        # ---- inference placement ----
-        self.inference = args.inference
-        if self.inference == "gpu" and self.device.type != "cuda":
-            self.inference = "cpu"
-        self.inference_proc: Optional[mp.Process] = None
         if self.inference == "gpu":
-            rows = args.num_actors * (2 if self.double_buffer else 1)
+            ctx = mp.get_context(self._mp_ctx)
+            rows = args.num_actors * self._pills_per_actor
             self.inf_slots = InferenceSlots(
                 rows, E, self.obs_shape, self.num_actions,
                 lstm_layers=2, lstm_hidden=lstm_hidden)
@@ -137,10 +113,7 @@ class ImpalaTrainer:
 
         # ---- learner state (device init deferred to setup()) ----
         self.learner_model: Optional[AtariNet] = None
-        self.global_step = 0
-        self.learn_iters = 0
-        self.timings = Timings()
-        self._pending = None  # in-flight prefetched batch token
+        self.remote_server = None
         self._graphed = None
         self.use_graph = bool(args.use_graph) and self.device.type == "cuda"
 
@@ -149,12 +122,8 @@ class ImpalaTrainer:
         if self._started:
             return
         args = self.args
-        env_spec = {"env_id": args.env_id,
-                    "envs_per_actor": args.envs_per_actor,
-                    "seed": args.seed + 7919 * self.rank}
-        ctx = mp.get_context(self._mp_ctx)
-
         if self.inference == "gpu":
+            ctx = mp.get_context(self._mp_ctx)
             model_kwargs = dict(observation_shape=self.obs_shape,
                                 num_actions=self.num_actions,
                                 use_lstm=args.use_lstm)
@@ -162,7 +131,7 @@ class ImpalaTrainer:
             wargs = (dev_index, model_kwargs, self.inf_slots,
                      self.shared_flat.flat, self.weights_version,
                      self.inf_req_q, self.inf_sems, self.stop_event)
-            if getattr(args, "inference_worker", "thread") == "thread":
+            if args.inference_worker == "thread":
                 import threading
                 self.inference_proc = threading.Thread(
                     target=inference_worker, args=wargs,
@@ -178,36 +147,31 @@ class ImpalaTrainer:
                     daemon=True, name=f"impala-infer-{self.rank}")
                 self.inference_proc.start()
 
-        for i in range(args.num_actors):
-            if self.double_buffer:
-                from ..parallel.rollout import actor_loop_db
-                target = actor_loop_db
-                kw = dict(seed=args.seed, episode_queue=self.episode_q,
-                          inf_slots=self.inf_slots,
-                          inf_req_q=self.inf_req_q,
-                          inf_sems=(self.inf_sems[2 * i],
-                                    self.inf_sems[2 * i + 1]),
-                          row_ids=(2 * i, 2 * i + 1))
+        super().start_actors()
+
+    def _actor_process(self, i: int):
+        args = self.args
+        env_spec = {"env_id": args.env_id,
+                    "envs_per_actor": args.envs_per_actor,
+                    "seed": args.seed + 7919 * self.rank}
+        kw = dict(seed=args.seed, episode_queue=self.episode_q)
+        if self.double_buffer:
+            target = actor_loop_db
+            kw.update(inf_slots=self.inf_slots, inf_req_q=self.inf_req_q,
+                      inf_sems=(self.inf_sems[2 * i],
+                                self.inf_sems[2 * i + 1]),
+                      row_ids=(2 * i, 2 * i + 1))
+        else:
+            target = actor_loop
+            if self.inference == "gpu":
+                kw.update(policy_factory=partial(
+                    remote_policy, self.inf_slots, self.inf_req_q,
+                    self.inf_sems[i]))
             else:
-                target = actor_loop
-                kw = dict(seed=args.seed, episode_queue=self.episode_q)
-                if self.inference == "gpu":
-                    kw.update(inf_slots=self.inf_slots,
-                              inf_req_q=self.inf_req_q,
-                              inf_sem=self.inf_sems[i])
-                else:
-                    kw.update(actor_model=self.actor_model)
-            p = ctx.Process(
-                target=target,
-                args=(i, env_spec, self.store, self.free_q, self.full_q,
-                      self.stop_event, self.step_counter),
-                kwargs=kw, daemon=True,
-                name=f"impala-actor-{self.rank}-{i}")
-            p.start()
-            self.actors.append(p)
-        for s in range(self.local_slots):
-            self.free_q.put(s)
-        self._started = True
+                kw.update(policy_factory=partial(local_policy,
+                                                 self.actor_model))
+        return (target, self._actor_args(i, env_spec), kw,
+                f"impala-actor-{self.rank}-{i}")
 
     def setup_learner(self) -> None:
         """Device-side init (safe to call after start_actors)."""
@@ -233,12 +197,7 @@ class ImpalaTrainer:
         if self.device.type == "cuda":
             # MIOpen exhaustive-find once per conv shape, then cached
             torch.backends.cudnn.benchmark = True
-            from ..parallel.rollout import PinRegistry
-            self._pins = PinRegistry()
-            pinned = self._pins.pin_store(self.store)
-            pinned += self._pins.pin(self.shared_flat.flat)
-            self.log.info(f"pinned {pinned/1e6:.1f} MB (rollout store + "
-                          f"shared weights)")
+            self._pin_host_memory()
             self.publish_stream = torch.cuda.Stream(device=self.device)
             self.publish_event = torch.cuda.Event()
         self._publish_weights()
@@ -263,7 +222,6 @@ class ImpalaTrainer:
         self._setup_remote_server()
 
     def _capture_graph(self) -> None:
-        from .graphed import GraphedImpalaStep
         args = self.args
         T, B = args.rollout_length, args.batch_size
         dev = self.device
@@ -285,10 +243,7 @@ class ImpalaTrainer:
                 2, 2, B, self.store.lstm_hidden, device=dev)
         self.log.info("capturing learner step into a hipGraph "
                       "(pre-actor-start) …")
-        self._graphed = GraphedImpalaStep(
-            self.learner_model, self.flat.flat_grad, self._loss_kwargs(),
-            synth, args.use_lstm, self.autocast_dtype,
-            args.reward_clipping == "abs_one", args.discounting)
+        self._graphed = self._graph_step(synth)
 
     def _setup_remote_server(self) -> None:
         # optional TCP server for remote-node actor farms
@@ -319,7 +274,7 @@ class ImpalaTrainer:
         (process mode only: thread-mode capture uses thread_local scope)."""
         if self.inference != "gpu":
             return
-        if getattr(self.args, "inference_worker", "thread") == "thread":
+        if self.args.inference_worker == "thread":
             return
         if pause:
             self.inf_pause.value = 1
@@ -352,109 +307,49 @@ class ImpalaTrainer:
                 self.weights_version.value += 1
 
     # -- core step ---------------------------------------------------------
-    def _get_full_slot(self, timeout_s: float = 30.0, max_wait_s: float = 600.0):
-        """full_q.get with a liveness watchdog: a dead actor or inference
-        worker turns a silent eternal hang into a fast, explicit error."""
-        import queue as _queue
-        waited = 0.0
-        while True:
-            try:
-                return self.full_q.get(timeout=timeout_s)
-            except _queue.Empty:
-                waited += timeout_s
-                dead = [p.name for p in self.actors if not p.is_alive()]
-                if dead:
-                    raise RuntimeError(f"actor process(es) died: {dead}")
-                if (self.inference_proc is not None
-                        and not self.inference_proc.is_alive()):
-                    raise RuntimeError("GPU inference worker died")
-                if waited >= max_wait_s:
-                    raise RuntimeError(
-                        f"no rollout slot arrived in {waited:.0f}s "
-                        f"(actors alive but not producing)")
-
-    def _start_prefetch(self):
-        slot_ids = [self._get_full_slot()
-                    for _ in range(self.slots_per_batch)]
-        self.timings.time("dequeue")
-        token = self.gatherer.start(slot_ids)
-        self.timings.time("gather_start")
-        return (token, slot_ids)
-
-    def next_batch(self) -> Dict[str, torch.Tensor]:
-        """Finish the pending prefetch (or do a cold gather) and kick off
-        the next one — batch N+1's H2D copies overlap batch N's compute."""
-        if self._pending is None:
-            self._pending = self._start_prefetch()
-        token, slot_ids = self._pending
-        batch = self.gatherer.finish(token)
-        self.timings.time("gather_wait")
-        for s in slot_ids:
-            if s >= self.local_slots:  # reserved remote-upload slot
-                self._free_remote_q.put(s)
-            else:
-                self.free_q.put(s)
-        self._pending = self._start_prefetch()
-        return batch
-
-    def _loss_kwargs(self) -> Dict[str, float]:
-        args = self.args
-        return dict(clip_rho_threshold=args.clip_rho_threshold,
-                    clip_c_threshold=1.0,
-                    clip_pg_rho_threshold=args.clip_pg_rho_threshold,
-                    baseline_cost=args.baseline_cost,
-                    entropy_cost=args.entropy_cost)
-
-    def _eager_fwd_bwd(self, batch):
-        args = self.args
-        model = self.learner_model
-        self.flat.flat_grad.zero_()
-        inputs = {"obs": batch["obs"], "reward": batch["reward"],
-                  "done": batch["done"], "last_action": batch["last_action"]}
-        core_state = ()
-        if args.use_lstm:
-            cs = batch["core_state"]
-            core_state = (cs[0], cs[1])
-        if self.autocast_dtype is not None:
-            with torch.autocast(device_type="cuda", dtype=self.autocast_dtype):
-                out, _ = model(inputs, core_state, greedy=True)
+    def _recycle_slot(self, slot: int) -> None:
+        if slot >= self.local_slots:  # reserved remote-upload slot
+            self._free_remote_q.put(slot)
         else:
-            out, _ = model(inputs, core_state, greedy=True)
-        logits = out["policy_logits"].float()
-        baseline = out["baseline"].float()
-        rewards = batch["reward"][1:]
-        if args.reward_clipping == "abs_one":
-            rewards = torch.clamp(rewards, -1, 1)
-        discounts = (~batch["done"][1:]).float() * args.discounting
-        total, comps, _ = impala_loss(
-            batch["logits"][:-1], logits[:-1], batch["action"][:-1],
-            rewards, discounts, baseline[:-1], baseline[-1].detach(),
-            **self._loss_kwargs())
-        self.timings.time("forward")
-        total.backward()
-        self.timings.time("backward")
-        return total.detach(), comps
+            self.free_q.put(slot)
+
+    def _fwd_bwd_kwargs(self) -> Dict:
+        """What :func:`graphed.impala_fwd_bwd` needs besides model, grads
+        and batch — the same for the eager and the captured step."""
+        args = self.args
+        return dict(
+            use_lstm=args.use_lstm, autocast_dtype=self.autocast_dtype,
+            reward_clip=args.reward_clipping == "abs_one",
+            discounting=args.discounting,
+            loss_kwargs=dict(
+                clip_rho_threshold=args.clip_rho_threshold,
+                clip_c_threshold=1.0,
+                clip_pg_rho_threshold=args.clip_pg_rho_threshold,
+                baseline_cost=args.baseline_cost,
+                entropy_cost=args.entropy_cost))
+
+    def _graph_step(self, batch_example) -> "graphed.GraphedImpalaStep":
+        return graphed.GraphedImpalaStep(
+            self.learner_model, self.flat.flat_grad, batch_example,
+            **self._fwd_bwd_kwargs())
 
     def learn_step(self, batch: Dict[str, torch.Tensor]) -> Dict[str, float]:
         args = self.args
         self.learner_model.train()
         if self.use_graph:
             if self._graphed is None:
-                from .graphed import GraphedImpalaStep
                 self.log.info("capturing learner step into a hipGraph …")
                 self._pause_inference(True)
                 try:
-                    self._graphed = GraphedImpalaStep(
-                        self.learner_model, self.flat.flat_grad,
-                        self._loss_kwargs(), batch, args.use_lstm,
-                        self.autocast_dtype,
-                        args.reward_clipping == "abs_one", args.discounting)
+                    self._graphed = self._graph_step(batch)
                 finally:
                     self._pause_inference(False)
             total, comps = self._graphed.run(batch)
             self.timings.time("graph_replay")
         else:
-            total, comps = self._eager_fwd_bwd(batch)
+            total, comps = graphed.impala_fwd_bwd(
+                self.learner_model, self.flat.flat_grad, batch,
+                timings=self.timings, **self._fwd_bwd_kwargs())
 
         all_reduce_flat(self.flat.flat_grad, average=True)
         clip_grad_norm_(self.flat.flat_grad, args.max_grad_norm)
@@ -485,9 +380,6 @@ class ImpalaTrainer:
         self.timings.reset()
         batch = self.next_batch()
         return self.learn_step(batch)
-
-    def reset_timings(self) -> None:
-        self.timings = Timings()
 
     # -- driver ------------------------------------------------------------
     def train(self) -> None:
@@ -597,11 +489,7 @@ class ImpalaTrainer:
         self.global_step = int(ckpt.get("global_step", 0))
         self._publish_weights()
 
-    def shutdown(self) -> None:
-        self.stop_event.set()
-        pills = len(self.actors) * (2 if self.double_buffer else 1)
-        for _ in range(pills):
-            self.free_q.put(None)  # poison pills (impala_atari.py:480)
+    def _before_join(self) -> None:
         if self.inference == "gpu":
             for s in self.inf_sems:
                 s.release()  # unblock any actor waiting on a response
@@ -609,15 +497,8 @@ class ImpalaTrainer:
                 self.inf_req_q.put_nowait(None)
             except Exception:
                 pass
-        # one shared grace period: an actor that is mid-rollout blocks on its
-        # inference semaphore once the worker is gone and never sees its
-        # pill, so a per-actor timeout would add up over all of them
-        deadline = time.time() + 2.0
-        for p in self.actors:
-            p.join(timeout=max(0.0, deadline - time.time()))
-            if p.is_alive():
-                p.terminate()
-        self.actors.clear()
+
+    def _after_join(self) -> None:
         if self.inference_proc is not None:
             self.inference_proc.join(timeout=2.0)
             if (self.inference_proc.is_alive()
@@ -625,11 +506,6 @@ class ImpalaTrainer:
                 self.inference_proc.terminate()  # Process only; a Thread
                 # is daemon and dies with us
             self.inference_proc = None
-        if getattr(self, "remote_server", None) is not None:
+        if self.remote_server is not None:
             self.remote_server.close()
             self.remote_server = None
-        if getattr(self, "_pins", None) is not None:
-            if self.device.type == "cuda":
-                torch.cuda.synchronize()
-            self._pins.unpin_all()
-            self._pins = None

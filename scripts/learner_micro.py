@@ -16,7 +16,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from scalerl_amd.models import AtariNet
-from scalerl_amd.ops import FusedRMSprop, clip_grad_norm_, impala_loss
+from scalerl_amd.ops import FusedRMSprop, clip_grad_norm_
 from scalerl_amd.parallel import FlatParams
 
 
@@ -54,47 +54,28 @@ def main():
         "action": torch.randint(0, A, (T + 1, B), device=dev),
         "logits": torch.randn(T + 1, B, A, device=dev),
     }
-    state = model.initial_state(B, device=dev) if args.use_lstm else ()
+    if args.use_lstm:
+        batch["core_state"] = torch.stack(model.initial_state(B, device=dev))
     autocast = (args.dtype == "bf16" and dev.type == "cuda")
+    # the trainer's own step, eager or captured (runtime/graphed.py)
+    from scalerl_amd.runtime.graphed import GraphedImpalaStep, impala_fwd_bwd
+    step_kwargs = dict(use_lstm=bool(args.use_lstm),
+                       autocast_dtype=torch.bfloat16 if autocast else None,
+                       reward_clip=True, discounting=0.99, loss_kwargs={})
+    if args.graph:
+        assert dev.type == "cuda", "--graph 1 needs a GPU"
+        fwd_bwd = GraphedImpalaStep(model, flat.flat_grad, batch,
+                                    **step_kwargs).run
+    else:
+        def fwd_bwd(b):
+            return impala_fwd_bwd(model, flat.flat_grad, b, **step_kwargs)
 
     def step():
-        flat.flat_grad.zero_()
-        inputs = {k: batch[k] for k in ("obs", "reward", "done", "last_action")}
-        if autocast:
-            with torch.autocast(device_type="cuda", dtype=torch.bfloat16):
-                out, _ = model(inputs, state, greedy=True)
-        else:
-            out, _ = model(inputs, state, greedy=True)
-        logits = out["policy_logits"].float()
-        baseline = out["baseline"].float()
-        total, comps, _ = impala_loss(
-            batch["logits"][:-1], logits[:-1], batch["action"][:-1],
-            torch.clamp(batch["reward"][1:], -1, 1),
-            (~batch["done"][1:]).float() * 0.99,
-            baseline[:-1], baseline[-1].detach())
-        total.backward()
+        total, _ = fwd_bwd(batch)
         clip_grad_norm_(flat.flat_grad, 40.0)
         opt.step(flat.flat_grad)
         pub.copy_(flat.flat, non_blocking=True)
         return total
-
-    if args.graph:
-        assert dev.type == "cuda", "--graph 1 needs a GPU"
-        from scalerl_amd.runtime.graphed import GraphedImpalaStep
-        example = dict(batch)
-        if args.use_lstm:
-            example["core_state"] = torch.stack(state)
-        # loss constants and flags as in step() above
-        graphed = GraphedImpalaStep(
-            model, flat.flat_grad, {}, example, bool(args.use_lstm),
-            torch.bfloat16 if autocast else None, True, 0.99)
-
-        def step():  # noqa: F811 — same work, fwd+bwd replayed from the graph
-            total, _ = graphed.run(example)
-            clip_grad_norm_(flat.flat_grad, 40.0)
-            opt.step(flat.flat_grad)
-            pub.copy_(flat.flat, non_blocking=True)
-            return total
 
     for _ in range(args.warmup):
         step()

@@ -170,6 +170,60 @@ def test_a3c_gpu_trainer_cpu_iteration():
         t.shutdown()
 
 
+def _one_actor_trainer(kind):
+    if kind == "apex":
+        from scalerl_amd.runtime.apex import ApexTrainer
+        return ApexTrainer(ApexArguments(
+            num_actors=1, envs_per_actor=4, buffer_size=4096, batch_size=64,
+            warmup_learn_steps=256, learner_update_times=1, device="cpu",
+            seed=3))
+    from scalerl_amd.config import A3CGpuArguments
+    from scalerl_amd.runtime.a3c_gpu import A3CGpuTrainer
+    return A3CGpuTrainer(A3CGpuArguments(
+        num_actors=1, envs_per_actor=4, rollout_steps=8, slots_per_batch=1,
+        device="cpu", seed=7, disable_checkpoint=True))
+
+
+@pytest.mark.parametrize("kind", ["apex", "a3c_gpu"])
+def test_dead_actor_raises_from_shared_watchdog(kind):
+    """Ape-X and A3C-GPU dequeue through the shared watchdog: dead actors
+    surface as an explicit error (A3C-GPU's own loop used to spin forever,
+    Ape-X's could fall out of its ingest loop with nothing ingested)."""
+    t = _one_actor_trainer(kind)
+    try:
+        t.start_actors()
+        t.setup_learner()
+        t.train_iteration()
+        for p in t.actors:
+            p.terminate()
+            p.join()
+        # drain whatever was already produced, then expect the watchdog
+        with pytest.raises(RuntimeError, match=r"actor process\(es\) died"):
+            for _ in range(t.store.num_slots + 2):
+                t._get_full_slot(timeout_s=0.5, max_wait_s=5.0)
+    finally:
+        t.shutdown()
+
+
+@pytest.mark.parametrize("kind", ["apex", "a3c_gpu"])
+def test_spawn_context_picklable(kind, monkeypatch):
+    """Everything handed to spawned actors must pickle, the policy factory
+    included (mirrors test_impala_spawn_context_picklable)."""
+    monkeypatch.setenv("SCALERL_FORCE_SPAWN", "1")
+    t = _one_actor_trainer(kind)
+    try:
+        assert t._mp_ctx == "spawn"
+        t.start_actors()
+        t.setup_learner()
+        stats = t.train_iteration()
+        if kind == "apex":
+            assert stats["ingested"] > 0  # a spawned actor filled a slot
+        else:
+            assert torch.isfinite(stats["total_loss"])
+    finally:
+        t.shutdown()
+
+
 @pytest.mark.gpu
 def test_a3c_gpu_trainer_on_gpu():
     """Config-2 path on hardware: CPU actors (42×42 stack) + GPU learner

@@ -225,6 +225,116 @@ def test_impala_gpu_graph_end_to_end(tmp_path):
         t.shutdown()
 
 
+def _learner_only(tmp_path, device, T=2, B=4):
+    """A trainer with its learner set up and no actors, for driving the
+    learner step on a hand-made batch."""
+    t = ImpalaTrainer(_args(tmp_path, rollout_length=T, batch_size=B,
+                            envs_per_actor=4, num_actors=1, device=device))
+    t.setup_learner()
+    t.learner_model.train()
+    return t
+
+
+def _fixed_batch(t, T=2, B=4):
+    g = torch.Generator(device="cpu").manual_seed(1234)
+    A = t.num_actions
+    return {
+        "obs": torch.randint(0, 256, (T + 1, B, 4, 84, 84), generator=g,
+                             dtype=torch.uint8),
+        "reward": torch.randn(T + 1, B, generator=g),
+        "done": torch.rand(T + 1, B, generator=g) < 0.25,
+        "last_action": torch.randint(0, A, (T + 1, B), generator=g),
+        "action": torch.randint(0, A, (T + 1, B), generator=g),
+        "logits": torch.randn(T + 1, B, A, generator=g),
+        "core_state": 0.1 * torch.randn(2, 2, B, t.store.lstm_hidden,
+                                        generator=g),
+    }
+
+
+def test_impala_eager_step_is_the_shared_fwd_bwd(tmp_path, monkeypatch):
+    """With use_graph off, learn_step reaches the loss through
+    graphed.impala_fwd_bwd — the function GraphedImpalaStep captures — and
+    the captured step holds no second copy of the maths."""
+    import inspect
+    from scalerl_amd.runtime import graphed
+    calls = []
+    real = graphed.impala_fwd_bwd
+
+    def counting(*a, **kw):
+        calls.append(kw.get("timings"))
+        return real(*a, **kw)
+
+    monkeypatch.setattr(graphed, "impala_fwd_bwd", counting)
+    t = _learner_only(tmp_path, "cpu")
+    try:
+        assert not t.use_graph
+        stats = t.learn_step(_fixed_batch(t))
+        assert len(calls) == 1 and calls[0] is t.timings
+        assert torch.isfinite(stats["total_loss"])
+        assert {"forward", "backward"} <= set(t.timings.means())
+    finally:
+        t.shutdown()
+    src = inspect.getsource(graphed.GraphedImpalaStep)
+    assert "impala_fwd_bwd(" in src
+    assert "impala_loss" not in src and ".backward(" not in src
+
+
+@pytest.mark.gpu
+def test_impala_graph_replay_equals_eager(tmp_path):
+    """The shared learner step (T=2, B=4, LSTM, fp32, one fixed batch, same
+    weights) run eagerly on the GPU and replayed through GraphedImpalaStep,
+    each held against the CPU fp32 result of the same function.
+
+    Bound: the parent commit's eager GPU step (its ``_eager_fwd_bwd``) was
+    measured against its own CPU fp32 result on this batch and these
+    weights, five repeats on one MI355X: largest absolute error 2.861e-06
+    (entropy loss, |ref| = 14.3), largest error relative to the largest
+    reference magnitude of the quantity 1.996e-07 (total loss; flat_grad:
+    1.49e-07 abs, 1.24e-07 rel).  Allowed here: 4× each, for every
+    quantity — MIOpen may pick another fp32 solver under capture, the
+    captured region uses the per-step LSTM driver, and atomics in the weight
+    gradient reorder sums.  Three replays are checked, not one.
+    """
+    from scalerl_amd.runtime import graphed
+    ABS, REL = 4 * 2.861e-06, 4 * 1.996e-07
+    cpu, gpu = _learner_only(tmp_path, "cpu"), _learner_only(tmp_path, "cuda:0")
+    try:
+        with torch.no_grad():
+            gpu.flat.flat.copy_(cpu.flat.flat)
+        batch = _fixed_batch(cpu)
+        dbatch = {k: v.to(gpu.device) for k, v in batch.items()}
+
+        def quantities(t, total, comps):
+            return {"total": total.reshape(1), "pg": comps[0:1],
+                    "baseline": comps[1:2], "entropy": comps[2:3],
+                    "flat_grad": t.flat.flat_grad}
+
+        ref = {k: v.detach().clone() for k, v in quantities(
+            cpu, *graphed.impala_fwd_bwd(cpu.learner_model, cpu.flat.flat_grad,
+                                         batch, **cpu._fwd_bwd_kwargs())).items()}
+
+        def check(what, total, comps):
+            for k, v in quantities(gpu, total, comps).items():
+                err = float((v.detach().cpu() - ref[k]).abs().max())
+                rel = err / float(ref[k].abs().max())
+                print(f"{what} {k}: abs={err:.3e} rel={rel:.3e}")
+                assert err <= ABS and rel <= REL, (what, k, err, rel)
+
+        check("eager", *graphed.impala_fwd_bwd(
+            gpu.learner_model, gpu.flat.flat_grad, dbatch,
+            **gpu._fwd_bwd_kwargs()))
+        try:
+            step = gpu._graph_step(dbatch)
+        except Exception as e:
+            pytest.skip(f"hipGraph capture fell back: {e!r}")
+        for i in range(3):
+            gpu.flat.flat_grad.fill_(7.0)  # the replay must zero it itself
+            check(f"replay {i}", *step.run(dbatch))
+    finally:
+        cpu.shutdown()
+        gpu.shutdown()
+
+
 @pytest.mark.gpu
 def test_impala_gpu_double_buffer_end_to_end(tmp_path):
     """SEED double-buffered actors (two env groups per actor) against the

@@ -13,7 +13,8 @@ from .frame_cast import frame_to_bf16
 from .lstm import MaskedLSTM
 from .optim import FusedAdam, FusedRMSprop, clip_grad_norm_, fused_polyak_
 from .per import SumTree
-from .scans import discounted_returns, gae, nstep_fold
+from .scans import (a2c_loss, a2c_loss_reference, discounted_returns, gae,
+                    nstep_fold)
 from .td import (c51_loss_reference, fused_c51_loss, fused_td_loss,
                  per_is_weights, td_loss_reference)
 from .ppo import ppo_fused_loss, ppo_loss_reference
@@ -29,5 +30,5 @@ __all__ = [
     "action_log_probs", "impala_loss", "impala_loss_reference",
     "vtrace_from_log_rhos", "vtrace_reference", "ppo_fused_loss",
     "ppo_loss_reference", "frame_to_bf16", "fused_encoder", "fused_c51_loss",
-    "c51_loss_reference",
+    "c51_loss_reference", "a2c_loss", "a2c_loss_reference",
 ]

@@ -70,7 +70,8 @@ _SIGNATURES = {
                          " float long long long f32 f32 f32 f32?",
     "vtrace_from_log_rhos": "f32 f32 f32 f32 f32 float float float long long"
                             " f32 f32",
-    "gae_scan": "f32 f32 f32 f32 float long long f32 f32",
+    "gae_scan": "f32 f32 f32 f32 float long long f32? f32? f32? i64? long float"
+                " float f32? f32? f32?",
     "discounted_returns": "f32 f32 f32? long long f32",
     "nstep_fold": "f32 f32 float long long long f32 f32 i32",
     "fused_rmsprop": "f32 f32 f32 f32? long float float float float float",

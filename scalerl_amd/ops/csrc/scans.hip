@@ -11,8 +11,10 @@
 //
 // All scans are sequential in T and parallel over the batch column: one
 // thread per column, grid-stride.  T*B is tiny (<= a few MB) — the win is
-// replacing a Python loop of eager ops with one launch.
+// replacing a Python loop of eager ops with one launch.  gae_scan also
+// carries the fused A2C loss of the A3C-GPU learner (see below).
 
+#include "a2c_loss.h"
 #include "common.h"
 
 extern "C" __global__ void gae_kernel(
@@ -37,10 +39,30 @@ extern "C" __global__ void gae_kernel(
   }
 }
 
+// Two modes, picked by `logits`:
+//   logits == null  plain scan: gae_kernel writes advantages and returns
+//                   (both required); actions, A, the coefficients and the
+//                   three trailing outputs are ignored.
+//   logits != null  fused A2C loss (a2c_loss.hip): the same scan out of LDS
+//                   plus the policy-gradient / value / entropy losses and
+//                   their gradients in one launch.  advantages and returns
+//                   are optional outputs; actions, grad_logits [T,B,A],
+//                   grad_values [T,B] and loss_out [3] (zeroed by the caller)
+//                   are required.  Returns -3 for T > A2C_MAX_T.
 extern "C" int gae_scan(const float* rewards, const float* values,
                         const float* bootstrap, const float* discounts,
                         float lam, long T, long B, float* advantages,
-                        float* returns, hipStream_t stream) {
+                        float* returns, const float* logits,
+                        const long* actions, long A, float value_coef,
+                        float entropy_coef, float* grad_logits,
+                        float* grad_values, float* loss_out,
+                        hipStream_t stream) {
+  if (logits)
+    return a2c_loss_launch(rewards, values, bootstrap, discounts, lam, T, B,
+                           advantages, returns, logits, actions, A, value_coef,
+                           entropy_coef, grad_logits, grad_values, loss_out,
+                           stream);
+  if (!advantages || !returns) return (int)hipErrorInvalidValue;
   const int block = 256;
   hipLaunchKernelGGL(gae_kernel, dim3(grid_1d(B, block)), dim3(block), 0,
                      stream, rewards, values, bootstrap, discounts, lam,

@@ -8,8 +8,13 @@ n-step — replay_buffer.py:230-273.
 from __future__ import annotations
 
 import torch
+import torch.nn.functional as F
 
 from ._backend import launch
+
+# the fused A2C loss stages 3 arrays of T*8 floats into 48 KiB of LDS
+# (csrc/a2c_loss.h: A2C_MAX_T)
+A2C_MAX_T = 512
 
 
 @torch.no_grad()
@@ -36,8 +41,108 @@ def gae(rewards, values, bootstrap_value, discounts, lam: float = 0.95):
     returns = torch.empty_like(r)
     launch("gae_scan", r, values.contiguous().float(),
            bootstrap_value.contiguous().float(),
-           discounts.contiguous().float(), lam, T, B, advantages, returns)
+           discounts.contiguous().float(), lam, T, B, advantages, returns,
+           None, None, 0, 0.0, 0.0, None, None, None)
     return advantages, returns
+
+
+def a2c_loss_reference(logits, values, bootstrap_value, actions, rewards,
+                       discounts, *, lam: float = 1.0,
+                       value_coef: float = 0.5, entropy_coef: float = 0.01):
+    """Composed autograd reference of the fused A2C loss (any device and
+    dtype): GAE on detached values, then policy gradient + value MSE +
+    entropy as means over [T,B].
+
+    Returns (total, components[3] = (pg, value, entropy) detached, returns).
+    """
+    with torch.no_grad():
+        adv, returns = gae(rewards, values.detach(), bootstrap_value.detach(),
+                           discounts, lam)
+    logp = F.log_softmax(logits, dim=-1)
+    taken = logp.gather(-1, actions.unsqueeze(-1)).squeeze(-1)
+    pg_loss = -(taken * adv).mean()
+    value_loss = 0.5 * F.mse_loss(values, returns)
+    entropy = -(logp.exp() * logp).sum(-1).mean()
+    total = pg_loss + value_coef * value_loss - entropy_coef * entropy
+    comps = torch.stack([pg_loss.detach(), value_loss.detach(),
+                         entropy.detach()])
+    return total, comps, returns
+
+
+class _A2CFusedLossFn(torch.autograd.Function):
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, logits, values, bootstrap_value, actions, rewards,
+                discounts, lam, value_coef, entropy_coef, want_returns):
+        T, B, A = logits.shape
+        # no zero-filled gradients for components and returns in backward
+        ctx.set_materialize_grads(False)
+        lg = logits.contiguous().float()
+        vals = values.contiguous().float()
+        # the kernel writes every element of both gradients
+        grad_logits = torch.empty_like(lg)
+        grad_values = torch.empty_like(vals)
+        loss_out = torch.zeros(3, device=lg.device, dtype=torch.float32)
+        returns = torch.empty_like(vals) if want_returns else None
+        launch("gae_scan", rewards.contiguous().float(), vals,
+               bootstrap_value.contiguous().float(),
+               discounts.contiguous().float(), float(lam), T, B, None, returns,
+               lg, actions.contiguous().long(), A, float(value_coef),
+               float(entropy_coef), grad_logits, grad_values, loss_out)
+        ctx.save_for_backward(grad_logits, grad_values)
+        total = (loss_out[0] + value_coef * loss_out[1]
+                 - entropy_coef * loss_out[2])
+        if returns is None:
+            returns = loss_out.new_zeros(0)
+        ctx.mark_non_differentiable(loss_out, returns)
+        return total, loss_out, returns
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, g_total, g_comps, g_returns):
+        if g_total is None:
+            return (None,) * 10
+        grad_logits, grad_values = ctx.saved_tensors
+        return (grad_logits * g_total, grad_values * g_total) + (None,) * 8
+
+
+def a2c_loss(logits, values, bootstrap_value, actions, rewards, discounts, *,
+             lam: float = 1.0, value_coef: float = 0.5,
+             entropy_coef: float = 0.01, want_returns: bool = False):
+    """GAE(lambda) actor-critic loss with autograd into ``logits`` [T,B,A]
+    and ``values`` [T,B].  GPU: one fused HIP launch (csrc/a2c_loss.hip), any
+    A >= 1, rollout length T <= ``A2C_MAX_T`` = 512 (the scan's LDS budget;
+    longer raises RuntimeError, code -3).  CPU: :func:`a2c_loss_reference`.
+
+    Advantages and returns are constants of the loss and ``bootstrap_value``
+    gets no gradient.  An action outside [0,A) makes the GPU loss and that
+    row's logits gradient NaN.
+
+    Returns (total, components[3] = (pg, value, entropy) means, returns [T,B]
+    or an empty tensor unless ``want_returns``).
+    """
+    if logits.dim() != 3:
+        raise ValueError(f"logits must be [T,B,A], got shape "
+                         f"{tuple(logits.shape)}")
+    T, B, A = logits.shape
+    if min(T, B, A) < 1:
+        raise ValueError(f"logits has an empty dimension: {(T, B, A)}")
+    for name, t in (("values", values), ("actions", actions),
+                    ("rewards", rewards), ("discounts", discounts)):
+        if tuple(t.shape) != (T, B):
+            raise ValueError(f"{name} has shape {tuple(t.shape)}, expected "
+                             f"{(T, B)}")
+    if tuple(bootstrap_value.shape) != (B,):
+        raise ValueError(f"bootstrap_value has shape "
+                         f"{tuple(bootstrap_value.shape)}, expected ({B},)")
+    if logits.is_cuda:
+        return _A2CFusedLossFn.apply(
+            logits, values, bootstrap_value, actions, rewards, discounts, lam,
+            value_coef, entropy_coef, want_returns)
+    total, comps, returns = a2c_loss_reference(
+        logits, values, bootstrap_value, actions, rewards, discounts, lam=lam,
+        value_coef=value_coef, entropy_coef=entropy_coef)
+    return total, comps, returns if want_returns else returns.new_zeros(0)
 
 
 @torch.no_grad()

@@ -7,10 +7,11 @@ shared-memory gradient publication does not scale to a GPU learner, so the
 MI355X design batches it: N CPU actor processes fill shared rollout slots
 (the IMPALA transport, parallel/rollout.py) with 42×42 float observations;
 the learner gathers K slots into a [T+1, K*E] batch, unrolls the
-A3CAtariNet over T with done-masked MaskedLSTM, computes GAE advantages on
-device (ops/scans.py HIP scan) and the A2C loss (policy gradient + value
-MSE + entropy), steps a fused Adam on the flat parameter buffer, and
-publishes weights back to the actors with one flat D2H copy.
+A3CAtariNet over T with done-masked MaskedLSTM, computes GAE advantages and
+the A2C loss (policy gradient + value MSE + entropy) with their gradients
+in one fused HIP launch (ops/scans.py ``a2c_loss``), steps a fused Adam on
+the flat parameter buffer, and publishes weights back to the actors with one
+flat D2H copy.
 
 The CPU-hogwild parity mode lives in :mod:`scalerl_amd.runtime.a3c`; this
 module is the GPU-scale path for the same algorithm family.
@@ -28,8 +29,7 @@ import torch.nn.functional as F
 
 from ..config import A3CGpuArguments
 from ..models.a3c_atari import A3CAtariNet
-from ..ops import FusedAdam, clip_grad_norm_
-from ..ops.scans import gae as gae_op
+from ..ops import FusedAdam, a2c_loss, clip_grad_norm_
 from ..parallel import FlatParams, all_reduce_flat
 from ..parallel.rollout import BatchGatherer, RolloutStore, actor_loop
 from ..utils.checkpoint import save_checkpoint
@@ -144,17 +144,10 @@ class A3CGpuTrainer(ActorLearnerTrainer):
         T = args.rollout_steps
         rewards = torch.clamp(batch["reward"][1:], -1, 1)  # r for action[t]
         discounts = notdone[1:] * args.gamma
-        with torch.no_grad():
-            adv, returns = gae_op(rewards, values[:-1].detach(),
-                                  values[-1].detach(), discounts,
-                                  args.gae_lambda)
-        logp = F.log_softmax(logits[:-1], dim=-1)
-        taken = logp.gather(-1, batch["action"][:-1].unsqueeze(-1)).squeeze(-1)
-        pg_loss = -(taken * adv).mean()
-        value_loss = 0.5 * F.mse_loss(values[:-1], returns)
-        entropy = -(logp.exp() * logp).sum(-1).mean()
-        total = (pg_loss + args.value_loss_coef * value_loss
-                 - args.entropy_coef * entropy)
+        total, comps, _ = a2c_loss(
+            logits[:-1], values[:-1], values[-1].detach(),
+            batch["action"][:-1], rewards, discounts, lam=args.gae_lambda,
+            value_coef=args.value_loss_coef, entropy_coef=args.entropy_coef)
         self.timings.time("forward")
         total.backward()
         self.timings.time("backward")
@@ -169,9 +162,8 @@ class A3CGpuTrainer(ActorLearnerTrainer):
         self.gatherer.mark_consumed()
         self.learn_iters += 1
         self.global_step += T * batch["action"].shape[1]
-        return {"total_loss": total.detach(), "pg_loss": pg_loss.detach(),
-                "value_loss": value_loss.detach(),
-                "entropy": entropy.detach()}
+        return {"total_loss": total.detach(), "pg_loss": comps[0],
+                "value_loss": comps[1], "entropy": comps[2]}
 
     def train_iteration(self) -> Dict[str, torch.Tensor]:
         batch = self.next_batch()

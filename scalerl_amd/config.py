@@ -146,6 +146,9 @@ class A3CGpuArguments(A3CArguments):
     learning_rate: float = 1e-4
     max_grad_norm: float = 50.0
     dtype: str = _h("learner compute dtype: bf16 | fp32", default="bf16")
+    fused_encoder: bool = _h(
+        "learner encoder forward (4 x conv3x3/2 + ELU) as one fused HIP "
+        "kernel; needs dtype bf16", default=False)
     total_steps: int = _h("total env steps", default=1_000_000)
     disable_checkpoint: bool = _h("skip periodic checkpoints", default=False)
     output_dir: str = _h("checkpoint directory", default="work_dirs/a3c_gpu")

@@ -8,6 +8,7 @@ numerics oracles in ``tests/``.
 
 from ._backend import available as kernels_available
 from ._backend import build as build_kernels
+from .a3c_encoder import fused_a3c_encoder
 from .encoder import fused_encoder
 from .frame_cast import frame_to_bf16
 from .lstm import MaskedLSTM
@@ -31,4 +32,5 @@ __all__ = [
     "vtrace_from_log_rhos", "vtrace_reference", "ppo_fused_loss",
     "ppo_loss_reference", "frame_to_bf16", "fused_encoder", "fused_c51_loss",
     "c51_loss_reference", "a2c_loss", "a2c_loss_reference",
+    "fused_a3c_encoder",
 ]

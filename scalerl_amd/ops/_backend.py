@@ -64,7 +64,6 @@ _CONV_FWD = "bf16 bf16 f32? bf16 long int"
 _CONV1_FWD_U8 = "u8 bf16 f32? bf16 long int"
 _CONV_WGRAD = "bf16 bf16 f32 long long"
 _CONV_WGRAD_V3 = "bf16 bf16 f32 long"
-_CONV_DGRAD = "bf16 bf16 bf16 long"
 _SIGNATURES = {
     "impala_fused_loss": "f32 f32 i64 f32 f32 f32 f32 float float float float"
                          " float long long long f32 f32 f32 f32?",
@@ -94,6 +93,8 @@ _SIGNATURES = {
     "frame_cast_u8_bf16": "u8 bf16 long",
     "mfma_selftest": "f32 f32 f32",
     "atari_encoder_fwd": "u8 bf16 f32 bf16 f32 bf16 f32 bf16? bf16? bf16 long",
+    "a3c_encoder_fwd": "f32 bf16 f32 bf16 f32 bf16 f32 bf16 f32 bf16? bf16?"
+                       " bf16? bf16 long int",
     "atari_conv1_fwd_u8": _CONV1_FWD_U8,
     "atari_conv1_fwd_bf16": _CONV_FWD,
     "atari_conv2_fwd": _CONV_FWD,
@@ -106,9 +107,8 @@ _SIGNATURES = {
     "atari_conv1_wgrad_v3": "u8 bf16 f32 long",
     "atari_conv2_wgrad_v3": _CONV_WGRAD_V3,
     "atari_conv3_wgrad_v3": _CONV_WGRAD_V3,
-    "atari_conv2_dgrad": _CONV_DGRAD,
-    "atari_conv3_dgrad": _CONV_DGRAD,
-    "atari_conv2_dgrad_v3": _CONV_DGRAD,
+    "atari_conv_dgrad": "bf16 bf16 bf16 long int",
+    "atari_conv2_dgrad_v3": "bf16 bf16 bf16 long",
 }
 
 _DTYPES = {"f32": torch.float32, "i64": torch.int64, "i32": torch.int32,
@@ -268,6 +268,8 @@ def launch(name: str, *args) -> None:
             hint = " (rollout length exceeds LDS budget)"
         elif ret == -4:
             hint = " (atom count outside the C51 kernel's 2..1024)"
+        elif ret == -5:
+            hint = " (input channels outside the A3C encoder's 1..4)"
         raise RuntimeError(
             f"HIP kernel {name} failed with code {ret}{hint}; "
             f"device={torch.cuda.get_device_name()}")

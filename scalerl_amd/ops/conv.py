@@ -105,9 +105,12 @@ def atari_conv_dgrad(layer: int, dout: torch.Tensor, weight: torch.Tensor,
     assert layer in ((2,) if v3 else _DGRAD_LAYERS)
     din = torch.empty((dout.shape[0], *_SHAPES[layer][0]),
                       dtype=torch.bfloat16, device=dout.device)
-    launch(f"atari_conv{layer}_dgrad" + ("_v3" if v3 else ""),
-           dout.to(torch.bfloat16).contiguous(),
-           weight.to(torch.bfloat16).contiguous(), din, dout.shape[0])
+    args = (dout.to(torch.bfloat16).contiguous(),
+            weight.to(torch.bfloat16).contiguous(), din, dout.shape[0])
+    if v3:
+        launch("atari_conv2_dgrad_v3", *args)
+    else:
+        launch("atari_conv_dgrad", *args, layer)
     return din
 
 

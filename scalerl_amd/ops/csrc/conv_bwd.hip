@@ -239,22 +239,23 @@ extern "C" int atari_conv3_wgrad(const void* in, const void* dout, float* dw,
   return 0;
 }
 
-extern "C" int atari_conv2_dgrad(const void* dout, const void* w, void* din,
-                                 long batch, hipStream_t stream) {
-  hipLaunchKernelGGL((convN_dgrad_v2<32, 4, 4, 2, 20, 20, 9, 9, 64, 1>),
-                     dim3((unsigned)batch), dim3(256), 0, stream,
-                     (const bf16_t*)dout, (const bf16_t*)w, (bf16_t*)din,
-                     (int)batch);
-  CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int atari_conv3_dgrad(const void* dout, const void* w, void* din,
-                                 long batch, hipStream_t stream) {
-  hipLaunchKernelGGL((convN_dgrad_v2<64, 3, 3, 1, 9, 9, 7, 7, 64, 2>),
-                     dim3((unsigned)((batch + 1) / 2)), dim3(256), 0, stream,
-                     (const bf16_t*)dout, (const bf16_t*)w, (bf16_t*)din,
-                     (int)batch);
+// The masked dgrad of conv2 or conv3, chosen by `layer` (conv1 is the input
+// layer and has none).
+extern "C" int atari_conv_dgrad(const void* dout, const void* w, void* din,
+                                long batch, int layer, hipStream_t stream) {
+  if (layer == 2) {
+    hipLaunchKernelGGL((convN_dgrad_v2<32, 4, 4, 2, 20, 20, 9, 9, 64, 1>),
+                       dim3((unsigned)batch), dim3(256), 0, stream,
+                       (const bf16_t*)dout, (const bf16_t*)w, (bf16_t*)din,
+                       (int)batch);
+  } else if (layer == 3) {
+    hipLaunchKernelGGL((convN_dgrad_v2<64, 3, 3, 1, 9, 9, 7, 7, 64, 2>),
+                       dim3((unsigned)((batch + 1) / 2)), dim3(256), 0, stream,
+                       (const bf16_t*)dout, (const bf16_t*)w, (bf16_t*)din,
+                       (int)batch);
+  } else {
+    return (int)hipErrorInvalidValue;
+  }
   CHECK_LAUNCH();
   return 0;
 }

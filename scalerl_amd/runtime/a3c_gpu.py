@@ -68,6 +68,10 @@ def a3c_local_policy(model: A3CAtariNet, actor_id: int,
 
 class A3CGpuTrainer(ActorLearnerTrainer):
     def __init__(self, args: A3CGpuArguments, device: Optional[str] = None):
+        if args.fused_encoder and args.dtype != "bf16":
+            raise ValueError(
+                f"fused_encoder computes in bf16 and needs dtype='bf16', got "
+                f"dtype={args.dtype!r}")
         super().__init__(args, device, "a3c-gpu")
 
         # probe the 42×42 wrapped env for shapes
@@ -104,8 +108,9 @@ class A3CGpuTrainer(ActorLearnerTrainer):
 
     def setup_learner(self) -> None:
         args = self.args
-        self.model = A3CAtariNet(self.obs_shape[0],
-                                 self.num_actions).to(self.device)
+        self.model = A3CAtariNet(
+            self.obs_shape[0], self.num_actions,
+            fused_encoder=args.fused_encoder).to(self.device)
         self.model.load_state_dict(self.actor_model.state_dict())
         self.flat = FlatParams(self.model, device=self.device)
         from ..parallel.dist import broadcast_flat, get_world_size as _ws

@@ -13,6 +13,7 @@
 // the s2 branch (zero when its clamp is saturated).
 
 #include "common.h"
+#include "policy_loss_wide.h"
 
 #define MAX_A 32
 
@@ -93,7 +94,10 @@ extern "C" int ppo_fused_loss(const float* logits, const long* actions,
                               long N, long A, float* grad_logits,
                               float* grad_values, float* loss_out,
                               hipStream_t stream) {
-  if (A > MAX_A) return -2;
+  if (A > MAX_A)
+    return ppo_loss_wide_launch(logits, actions, old_logp, adv, returns,
+                                values, clip_eps, vcoef, ecoef, N, A,
+                                grad_logits, grad_values, loss_out, stream);
   const int block = 256;
   hipLaunchKernelGGL(ppo_fused_loss_kernel, dim3(grid_1d(N, block)),
                      dim3(block), 0, stream, logits, actions, old_logp, adv,

@@ -19,6 +19,7 @@
 //   total = pg + baseline_cost * baseline + entropy_cost * entropy.
 
 #include "common.h"
+#include "policy_loss_wide.h"
 
 #define MAX_A 32  // Atari action sets are <= 18
 
@@ -151,7 +152,11 @@ extern "C" int impala_fused_loss(
     long T, long B, long A,
     float* grad_logits, float* grad_values, float* loss_out, float* vs_out,
     hipStream_t stream) {
-  if (A > MAX_A) return -2;
+  if (A > MAX_A)
+    return impala_loss_wide_launch(
+        behavior_logits, target_logits, actions, rewards, discounts, values,
+        bootstrap, clip_rho, clip_c, clip_pg_rho, baseline_cost, entropy_cost,
+        T, B, A, grad_logits, grad_values, loss_out, vs_out, stream);
   const size_t smem = (4 * (size_t)T + 16) * sizeof(float);
   if (smem > 160 * 1024) return -3;
   hipLaunchKernelGGL(impala_fused_loss_kernel, dim3((int)B), dim3(256), smem,

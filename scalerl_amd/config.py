@@ -106,6 +106,11 @@ class DQNArguments(RLArguments):
     v_min: float = _h("C51 value-support min", default=-10.0)
     v_max: float = _h("C51 value-support max", default=10.0)
     num_atoms: int = _h("C51 atoms", default=51)
+    quantile_dqn: bool = _h("QR-DQN quantile head (not with categorical_dqn)",
+                            default=False)
+    num_quantiles: int = _h("QR-DQN quantiles per action", default=200)
+    huber_kappa: float = _h("QR-DQN quantile-Huber threshold κ (> 0)",
+                            default=1.0)
     eps_greedy_start: float = _h("initial exploration epsilon", default=1.0)
     eps_greedy_end: float = _h("final exploration epsilon", default=0.1)
     eps_decay_steps: int = _h("steps for linear epsilon decay", default=50_000)

@@ -249,3 +249,42 @@ class CategoricalAtariQNet(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """Expected Q-values [B, A]."""
         return (self.dist(x).exp() * self.support).sum(-1)
+
+
+class QuantileAtariQNet(nn.Module):
+    """QR-DQN quantile Q-network on the Nature-CNN body.  Same
+    ``quantiles``/``forward`` surface as
+    :class:`scalerl_amd.models.noisy.QuantileQNet`, so ``qr_loss`` works
+    against either."""
+
+    def __init__(self, observation_shape=(4, 84, 84), num_actions: int = 6,
+                 num_quantiles: int = 200, noisy: bool = False):
+        super().__init__()
+        from .noisy import NoisyLinear
+        c = observation_shape[0]
+        self.action_dim = self.num_actions = num_actions
+        self.num_quantiles = num_quantiles
+        self.noisy = noisy
+        lin = NoisyLinear if noisy else nn.Linear
+        self.conv1 = nn.Conv2d(c, 32, kernel_size=8, stride=4)
+        self.conv2 = nn.Conv2d(32, 64, kernel_size=4, stride=2)
+        self.conv3 = nn.Conv2d(64, 64, kernel_size=3, stride=1)
+        self.fc = nn.Linear(64 * 7 * 7, 512)
+        self.head = lin(512, num_actions * num_quantiles)
+
+    def reset_noise(self):
+        from .noisy import reset_noise
+        reset_noise(self)
+
+    def quantiles(self, x: torch.Tensor) -> torch.Tensor:
+        """→ quantile values [B, A, N]."""
+        x = x.float() / 255.0
+        x = F.relu(self.conv1(x))
+        x = F.relu(self.conv2(x))
+        x = F.relu(self.conv3(x))
+        h = F.relu(self.fc(torch.flatten(x, 1)))
+        return self.head(h).view(-1, self.num_actions, self.num_quantiles)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """Expected Q-values [B, A]: the mean over the quantiles."""
+        return self.quantiles(x).mean(-1)

@@ -1,9 +1,10 @@
-"""NoisyNet linear layer + C51 categorical Q-network.
+"""NoisyNet linear layer + C51 categorical and QR-DQN quantile Q-networks.
 
 The reference declares ``noisy_dqn`` / ``categorical_dqn`` flags with
 v_min/v_max/atoms hyperparams (rl_args.py:163-315) but ships no
 implementation; these implement the published semantics (Fortunato et al.
-2018 factorised-Gaussian NoisyNet; Bellemare et al. 2017 C51)."""
+2018 factorised-Gaussian NoisyNet; Bellemare et al. 2017 C51; Dabney et al.
+2018 QR-DQN, which the reference does not declare)."""
 
 from __future__ import annotations
 
@@ -122,3 +123,53 @@ def c51_loss(net: CategoricalQNet, target_net: CategoricalQNet, obs, actions,
                           discounts, net.v_min, net.v_max, prios=prios,
                           p_total=p_total, p_min=p_min, beta=beta,
                           replay_size=replay_size)
+
+
+class QuantileQNet(nn.Module):
+    """QR-DQN Q-network: ``num_quantiles`` quantile values per action."""
+
+    def __init__(self, obs_dim: int, action_dim: int, hidden_dim: int = 128,
+                 num_quantiles: int = 200, noisy: bool = False):
+        super().__init__()
+        self.action_dim = action_dim
+        self.num_quantiles = num_quantiles
+        lin = NoisyLinear if noisy else nn.Linear
+        self.body = nn.Sequential(
+            nn.Linear(obs_dim, hidden_dim), nn.ReLU(),
+            nn.Linear(hidden_dim, hidden_dim), nn.ReLU())
+        self.head = lin(hidden_dim, action_dim * num_quantiles)
+
+    def quantiles(self, obs: torch.Tensor) -> torch.Tensor:
+        """→ quantile values [B, A, N]."""
+        h = self.body(obs)
+        return self.head(h).view(-1, self.action_dim, self.num_quantiles)
+
+    def forward(self, obs: torch.Tensor) -> torch.Tensor:
+        """Expected Q-values [B, A]: the mean over the quantiles."""
+        return self.quantiles(obs).mean(-1)
+
+
+def qr_loss(net, target_net, obs, actions, rewards, discounts, next_obs,
+            double: bool = True, kappa: float = 1.0, weights=None, *,
+            prios=None, p_total=None, p_min=None, beta: float = 0.4,
+            replay_size: int = 0):
+    """Quantile-Huber TD loss (Dabney et al. 2018, alg. 1).
+
+    Returns (loss scalar, priorities = per-sample loss).  The nets only
+    produce quantile values (``.quantiles(obs)``); the loss itself is
+    :func:`scalerl_amd.ops.fused_qr_loss` — one HIP kernel on the GPU, the
+    composed reference on the CPU.  ``prios`` and ``weights`` as in
+    :func:`c51_loss`."""
+    from ..ops.td import fused_qr_loss, qr_loss_reference
+    if weights is not None and prios is not None:
+        raise ValueError("pass either weights or prios, not both")
+    with torch.no_grad():
+        next_online = net.quantiles(next_obs) if double else None
+        next_target = target_net.quantiles(next_obs)
+    theta = net.quantiles(obs)
+    if weights is not None:
+        return qr_loss_reference(theta, next_online, next_target, actions,
+                                 rewards, discounts, kappa, weights)
+    return fused_qr_loss(theta, next_online, next_target, actions, rewards,
+                         discounts, kappa, prios=prios, p_total=p_total,
+                         p_min=p_min, beta=beta, replay_size=replay_size)

@@ -16,8 +16,9 @@ from .optim import FusedAdam, FusedRMSprop, clip_grad_norm_, fused_polyak_
 from .per import SumTree
 from .scans import (a2c_loss, a2c_loss_reference, discounted_returns, gae,
                     nstep_fold)
-from .td import (c51_loss_reference, fused_c51_loss, fused_td_loss,
-                 per_is_weights, td_loss_reference)
+from .td import (c51_loss_reference, fused_c51_loss, fused_qr_loss,
+                 fused_td_loss, per_is_weights, qr_loss_reference,
+                 td_loss_reference)
 from .ppo import ppo_fused_loss, ppo_loss_reference
 from .vtrace import (VTraceReturns, action_log_probs, impala_loss,
                      impala_loss_reference, vtrace_from_log_rhos,
@@ -32,5 +33,5 @@ __all__ = [
     "vtrace_from_log_rhos", "vtrace_reference", "ppo_fused_loss",
     "ppo_loss_reference", "frame_to_bf16", "fused_encoder", "fused_c51_loss",
     "c51_loss_reference", "a2c_loss", "a2c_loss_reference",
-    "fused_a3c_encoder",
+    "fused_a3c_encoder", "fused_qr_loss", "qr_loss_reference",
 ]

@@ -267,7 +267,8 @@ def launch(name: str, *args) -> None:
         elif ret == -3:
             hint = " (rollout length exceeds LDS budget)"
         elif ret == -4:
-            hint = " (atom count outside the C51 kernel's 2..1024)"
+            hint = (" (atom count outside the C51 kernel's, or quantile "
+                    "count outside the QR kernel's, 2..1024)")
         elif ret == -5:
             hint = " (input channels outside the A3C encoder's 1..4)"
         raise RuntimeError(

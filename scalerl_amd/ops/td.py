@@ -7,8 +7,15 @@ MSE), apex/worker.py:134-161 (IS weights, priority update).
 Categorical (C51, Bellemare et al. 2017 alg. 1): greedy next action from the
 expected Q, projection of the target distribution onto the support, cross
 entropy against the online row, the same IS weights, per-sample cross entropy
-as the new priorities.  Both go through the one ``fused_td_loss`` entry point
-of ``csrc/td_loss.hip``.
+as the new priorities.
+
+Quantile regression (QR-DQN, Dabney et al. 2018 alg. 1): greedy next action
+from the mean of the quantiles, the N x N pairwise quantile-Huber terms
+between the Bellman targets and the online quantiles, the same IS weights,
+per-sample loss as the new priorities.
+
+All three go through the one ``fused_td_loss`` entry point of
+``csrc/td_loss.hip``.
 """
 
 from __future__ import annotations
@@ -206,3 +213,106 @@ def fused_c51_loss(logits, next_logits_online, next_logits_target, actions,
     return c51_loss_reference(logits, next_logits_online, next_logits_target,
                               actions, rewards, discounts, v_min, v_max,
                               weights)
+
+
+def qr_loss_reference(theta, next_online, next_target, actions, rewards,
+                      discounts, kappa=1.0, weights=None):
+    """Autograd-capable composed QR-DQN quantile-Huber loss on raw quantile
+    values [B,A,N], in the dtype of its inputs (fp64 inputs make it the
+    oracle).  Returns (loss, per-sample loss detached).  ``next_online`` None
+    selects the greedy action with the target net (vanilla DQN)."""
+    B, _, N = theta.shape
+    rows = torch.arange(B, device=theta.device)
+    with torch.no_grad():
+        sel = next_online if next_online is not None else next_target
+        astar = sel.mean(dim=-1).argmax(dim=1)
+        target = (rewards.unsqueeze(1)
+                  + discounts.unsqueeze(1) * next_target[rows, astar])
+        tau = ((torch.arange(N, device=theta.device, dtype=theta.dtype) + 0.5)
+               / N)
+    pred = theta[rows, actions]                               # [B, N] (i)
+    u = target.unsqueeze(1) - pred.unsqueeze(2)               # [B, i, j]
+    au = u.abs()
+    huber = torch.where(au <= kappa, 0.5 * u * u,
+                        kappa * (au - 0.5 * kappa))
+    rho = (tau.view(1, N, 1) - (u.detach() < 0).to(theta.dtype)).abs() \
+        * huber / kappa
+    ql = rho.mean(dim=2).sum(dim=1)
+    loss = (ql * weights).mean() if weights is not None else ql.mean()
+    return loss, ql.detach()
+
+
+class _FusedQRLossFn(torch.autograd.Function):
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, theta, next_online, next_target, actions, rewards,
+                discounts, prios, p_total, p_min, beta, replay_size, kappa):
+        B, A, N = theta.shape
+        # no zero-filled gradient for the non-differentiable ql in backward
+        ctx.set_materialize_grads(False)
+        tc = theta.contiguous().float()
+        grad = torch.empty_like(tc)  # the kernel writes every element
+        ql = torch.empty(B, device=tc.device, dtype=torch.float32)
+        loss_out = torch.zeros(1, device=tc.device, dtype=torch.float32)
+        # huber == 2 with atoms == N selects qr_loss_kernel; kappa travels as
+        # huber_delta, v_min/v_max are unused
+        launch("fused_td_loss", tc,
+               next_online.contiguous().float()
+               if next_online is not None else None,
+               next_target.contiguous().float(),
+               actions.contiguous().long(), rewards.contiguous().float(),
+               discounts.contiguous().float(), prios, p_total, p_min,
+               float(beta), int(replay_size), B, A, 2, float(kappa), N, 0.0,
+               0.0, grad, ql, loss_out)
+        ctx.save_for_backward(grad)
+        ctx.mark_non_differentiable(ql)
+        return loss_out[0], ql
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, g_loss, g_ql):
+        if g_loss is None:
+            return (None,) * 12
+        (grad,) = ctx.saved_tensors
+        return (grad * g_loss,) + (None,) * 11
+
+
+def fused_qr_loss(theta, next_online, next_target, actions, rewards,
+                  discounts, kappa: float = 1.0, *, prios=None, p_total=None,
+                  p_min=None, beta: float = 0.4, replay_size: int = 0
+                  ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """QR-DQN quantile-Huber loss on raw quantile values [B,A,N].  Returns
+    (loss scalar w/ autograd into ``theta``, per-sample loss [B] — the new
+    priorities)."""
+    if theta.dim() != 3:
+        raise ValueError(f"theta must be [B,A,quantiles], got shape "
+                         f"{tuple(theta.shape)}")
+    B, A, N = theta.shape
+    if N < 2:
+        raise ValueError(f"QR-DQN needs at least 2 quantiles, got {N}")
+    if not kappa > 0:
+        raise ValueError(f"kappa must be positive, got {kappa}")
+    for name, t in (("next_online", next_online),
+                    ("next_target", next_target)):
+        if t is None and name == "next_online":
+            continue
+        if tuple(t.shape) != (B, A, N):
+            raise ValueError(f"{name} has shape {tuple(t.shape)}, theta "
+                             f"{(B, A, N)}: batch, actions and quantiles "
+                             f"must match")
+    for name, t in (("actions", actions), ("rewards", rewards),
+                    ("discounts", discounts), ("prios", prios)):
+        if t is not None and tuple(t.shape) != (B,):
+            raise ValueError(f"{name} has shape {tuple(t.shape)}, expected "
+                             f"({B},)")
+    if prios is not None and (p_total is None or p_min is None):
+        raise ValueError("prios needs p_total and p_min")
+    if theta.is_cuda:
+        return _FusedQRLossFn.apply(
+            theta, next_online, next_target, actions, rewards, discounts,
+            prios, p_total, p_min, beta, replay_size, kappa)
+    weights = None
+    if prios is not None:
+        weights = per_is_weights(prios, p_total, p_min, replay_size, beta)
+    return qr_loss_reference(theta, next_online, next_target, actions,
+                             rewards, discounts, kappa, weights)

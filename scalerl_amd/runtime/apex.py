@@ -87,6 +87,10 @@ class ApexTrainer(ActorLearnerTrainer):
         E = args.envs_per_actor
         self.chunk_len = 32  # transitions per slot row-block
         self.categorical = getattr(args, "categorical_dqn", False)
+        self.quantile = getattr(args, "quantile_dqn", False)
+        if self.quantile and self.categorical:
+            raise ValueError("quantile_dqn and categorical_dqn are two "
+                             "different distributional heads: set one")
         # CPU phase (precedes any HIP initialization)
         torch.manual_seed(args.seed + self.rank)
         self.actor_model = self._build_qnet()
@@ -100,6 +104,11 @@ class ApexTrainer(ActorLearnerTrainer):
 
     def _build_qnet(self):
         args = self.args
+        if self.quantile:
+            from ..models.atari import QuantileAtariQNet
+            return QuantileAtariQNet(
+                self.obs_shape, self.num_actions,
+                num_quantiles=args.num_quantiles, noisy=args.noisy_dqn)
         if self.categorical:
             from ..models.atari import CategoricalAtariQNet
             return CategoricalAtariQNet(
@@ -243,7 +252,16 @@ class ApexTrainer(ActorLearnerTrainer):
                 batch = self.buffer.sample(args.batch_size)
                 per_kw = {}
             self.flat.flat_grad.zero_()
-            if self.categorical:
+            if self.quantile:
+                # QR-DQN quantile-Huber loss (Dabney et al. 2018); IS
+                # weights as below, priorities ← per-sample loss
+                from ..models.noisy import qr_loss
+                loss, td_abs = qr_loss(
+                    self.model, self.target_model, batch["obs"],
+                    batch["action"], batch["reward"], batch["discount"],
+                    batch["next_obs"], double=args.double_dqn,
+                    kappa=args.huber_kappa, **per_kw)
+            elif self.categorical:
                 # C51 projection loss (Bellemare et al. 2017); IS weights
                 # from the sampled priorities, priorities ← per-sample KL
                 from ..models.noisy import c51_loss

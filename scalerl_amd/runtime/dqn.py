@@ -37,9 +37,18 @@ class DQNAgent(BaseAgent):
         self.device = torch.device(device)
         self.action_dim = action_dim
         self.categorical = args.categorical_dqn
+        self.quantile = args.quantile_dqn
+        if self.quantile and self.categorical:
+            raise ValueError("quantile_dqn and categorical_dqn are two "
+                             "different distributional heads: set one")
         self.noisy = args.noisy_dqn
 
         def build():
+            if self.quantile:
+                from ..models.noisy import QuantileQNet
+                return QuantileQNet(obs_dim, action_dim, args.hidden_dim,
+                                    num_quantiles=args.num_quantiles,
+                                    noisy=self.noisy)
             if self.categorical:
                 from ..models.noisy import CategoricalQNet
                 return CategoricalQNet(obs_dim, action_dim, args.hidden_dim,
@@ -96,7 +105,7 @@ class DQNAgent(BaseAgent):
         discounts = batch["discount"].to(self.device)
 
         self.flat.flat_grad.zero_()
-        if not self.categorical:
+        if not (self.categorical or self.quantile):
             self.model.train()
             q = self.model(obs)
             with torch.no_grad():
@@ -107,7 +116,15 @@ class DQNAgent(BaseAgent):
         p_total = p_min = None
         if prios is not None and hasattr(self, "_per_stats"):
             p_total, p_min = self._per_stats
-        if self.categorical:
+        if self.quantile:
+            from ..models.noisy import qr_loss
+            self.model.train()
+            loss, td_abs = qr_loss(
+                self.model, self.target_model, obs, actions, rewards,
+                discounts, next_obs, double=args.double_dqn,
+                kappa=args.huber_kappa, prios=prios, p_total=p_total,
+                p_min=p_min, beta=self.per_beta, replay_size=replay_size)
+        elif self.categorical:
             from ..models.noisy import c51_loss
             self.model.train()
             loss, td_abs = c51_loss(
